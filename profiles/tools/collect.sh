@@ -14,8 +14,8 @@ ARGS="$*"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/${round}_$tag
 mkdir -p $out
-python bench.py --steps 20 --warmup 3 > $out/bench_cfg4.json 2> $out/bench_cfg4.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python bench.py --steps 5 --warmup 2 --passes 1 --no-strong --no-cpu-baseline --no-mode-sweep --no-side-stream > $out/bench_under_rocprof.json 2> $out/prof.err
+python bench.py --full --steps 20 --warmup 3 > $out/bench_cfg4.json 2> $out/bench_cfg4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python bench.py --full --steps 5 --warmup 2 --passes 1 --no-strong --no-cpu-baseline --no-mode-sweep --no-side-stream > $out/bench_under_rocprof.json 2> $out/prof.err
 rm -f $out/prof/*/p_kernel_trace.csv $out/prof/p_kernel_trace.csv
 stats=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 python profiles/summarize.py stats $stats auto > $out/per_step_table.txt
@@ -33,7 +33,7 @@ if want full; then
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -o p -- python bench.py --steps 2 --warmup 1 $quiet > $out/pmc_write.log 2>&1
   rm -f $out/pmc_*/p_kernel_trace.csv $out/pmc_*/*/p_kernel_trace.csv
   # (20 warm-up steps: the launch-bound configs 1 and 2 speed up by 10 % over the first passes of a process)
-  for c in 1 2 3 5; do python bench.py --config $c --steps 20 --warmup 20 > $out/bench_cfg$c.json 2> $out/bench_cfg$c.err; done
+  for c in 1 2 3 5; do python bench.py --full --config $c --steps 20 --warmup 20 > $out/bench_cfg$c.json 2> $out/bench_cfg$c.err; done
   f=$(find $out/pmc_fetch -name "*counter_collection.csv" | head -1); w=$(find $out/pmc_write -name "*counter_collection.csv" | head -1)
   alg=$(python -c "import json; print(json.load(open('$out/bench_cfg4.json'))['roofline']['gemm_family']['algorithmic_bytes_per_launch'])")
   python profiles/summarize.py traffic $f $w $alg $out/gemm_hbm_traffic.json > /dev/null

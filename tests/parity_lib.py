@@ -10,17 +10,21 @@ import numpy as np
 import torch
 
 _POOL = None
+# Every worker is a process that imports torch; with the test process, the data-parallel tests' two ranks and a subprocess
+# beside it, the suite stays below 16 such processes at any time, however many cores the host reports.
+POOL_WORKERS_MAX = 8
 
 
 def cpu_pool():
     """A spawn pool for the CPU side of the parity tests (round 6: the fp64 NeRF builds of the parity record - Python loops
-    over chains of up to 1500 residues - ran one after the other and were 260 s of the GPU suite); one per test process."""
+    over chains of up to 1500 residues - ran one after the other and were 260 s of the GPU suite); one per test process,
+    shared by every test that needs one."""
     global _POOL
     if _POOL is None:
         import atexit
         import multiprocessing as mp
         import os
-        n = max(1, min(16, (os.cpu_count() or 2) // 2))
+        n = max(1, min(POOL_WORKERS_MAX, (os.cpu_count() or 2) // 2))
         _POOL = mp.get_context("spawn").Pool(n, initializer=torch.set_num_threads, initargs=(1,))
         atexit.register(_POOL.terminate)
     return _POOL

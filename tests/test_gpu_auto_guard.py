@@ -220,10 +220,8 @@ def test_adversarial_ranges(dev, what):
         assert not guard.off.any() and not guard.wide.any()
 
 
-# (round 6: these trajectories are `slow` - out of the default `-m gpu` run, whose limit on the driver's box is 1200 s: they
-# took 387 s of a 976-s suite on one box and, at a fifth of the steps, still 270 s on a box with slower host cores; run them
-# with --runslow / PTAMD_RUN_SLOW=1, record under profiles/.  Every single-step oracle comparison stays in the default run.)
-@pytest.mark.slow
+# (the longest tests of the suite: the fp64 oracle's steps on the host set their time - 170 s for the four on a host with fast
+# cores, up to twice that where the cores are slower)
 @pytest.mark.parametrize("optimizer,lr,default_steps", [("adam", 1e-4, 200), ("sgd", 1e-2, 60), ("adam", 1e-4, 40), ("sgd", 1e-2, 20)])
 def test_moved_weights_trajectory(dev, optimizer, lr, default_steps):
     """BASELINE config-2 model (d256, 4 layers, 8 heads, dff 2048); 8 proteins x L <= 64 so that the fp64 oracle - a Python

@@ -204,9 +204,8 @@ def test_config4_full_size_auto_steady_state(dev):
     # arctanh of realistic angle means, as the parity record's "realistic" draws): on the arbitrary angles of the model above
     # some protein always holds a near-straight bond angle, and there ANY two fp32 chains differ by tens of per cent in the
     # gradient (measured: 0.58 for AUTO and for the exact three-term arithmetic alike).
-    import multiprocessing as mp
-    import os
     from oracle import step as ostep
+    from parity_lib import cpu_pool
     from test_gpu_parity_record import realistic_angle_means
     model = _model(dev, 6, 8, 512, 2048, L, realistic_angle_means(19), seed=7)
     with torch.no_grad():
@@ -220,10 +219,8 @@ def test_config4_full_size_auto_steady_state(dev):
     g_b3, _ = run(K_.GEMM_BF16X3)
     model.gemm_mode = None
     params = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    workers = max(1, min(32, os.cpu_count() or 1))
-    with mp.get_context("spawn").Pool(workers, initializer=torch.set_num_threads, initargs=(1,)) as pool:
-        ref = ostep.CpuTrainer(params, 8, loss="drmsd", optimizer="sgd", lr=1e-4, clip=None, pool=pool)
-        ref.step(seq.cpu(), ang.cpu(), crd.cpu(), keep_grads=True)
+    ref = ostep.CpuTrainer(params, 8, loss="drmsd", optimizer="sgd", lr=1e-4, clip=None, pool=cpu_pool())
+    ref.step(seq.cpu(), ang.cpu(), crd.cpu(), keep_grads=True)
     d_ref, ln_ref = float(ref.last_losses["drmsd-full"]), float(ref.last_losses["lndrmsd-full"])
     e_orc, t_orc = per_group({n: g.cpu() for n, g in g_auto.items()}, ref.last_grads)
     e_orc3, t_orc3 = per_group({n: g.cpu() for n, g in g_b3.items()}, ref.last_grads)

@@ -368,15 +368,10 @@ def _bars(draws):
 
 
 def _cases_by_regime():
-    """(case, regime) pairs; config 5 in the ARBITRARY regime is `slow` (round 6): 72 % of its L = 1500 draws are ill-conditioned for
-    any fp32 chain and skipped - the test spends its time filtering (74 s on a fast host, 270 s on a slow one) - while the realistic
-    regime, asserted as SURVEY 8(d) is written, stays in the default run; the committed record (parity_seeds.sh) has both."""
-    out = []
-    for c in CASES:
-        for regime in ("arbitrary", "realistic"):
-            marks = [pytest.mark.slow] if (c[0] == 5 and regime == "arbitrary" and "PTAMD_PARITY_SEEDS" not in os.environ) else []
-            out.append(pytest.param(c, regime, id=f"{regime}-config{c[0]}", marks=marks))
-    return out
+    """(case, regime) pairs, every configuration in both regimes.  Config 5 in the ARBITRARY regime is the longest of them: 72 %
+    of its L = 1500 draws are ill-conditioned for any fp32 chain and skipped - the test spends its time filtering (74 s on a
+    fast host, 270 s on a slow one); the committed record (parity_seeds.sh) takes more draws of both regimes."""
+    return [pytest.param(c, regime, id=f"{regime}-config{c[0]}") for c in CASES for regime in ("arbitrary", "realistic")]
 
 
 @pytest.mark.parametrize("case,regime", _cases_by_regime())
