@@ -565,22 +565,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
 // tile - the staging that was a fifth of the kernel's VALU instructions (profiles/tools/isa_mix.py: 570 -> 491 per tile and
 // wavefront, all paths).  Same scaling groups, same split arithmetic, same soft-max, same dropout decisions: bit-identical to
 // attn_fwd_f16x2_kernel<64, 8, 1> on the fp32 K / V those planes were made from.
-// A stage is TPS tiles (TPS x 32 keys): THREE stage buffers, the pieces of stage s + 2 issued at the end of stage s and a
+// A stage is TPS = 2 tiles (64 keys): THREE stage buffers, the pieces of stage s + 2 issued at the end of stage s and a
 // counted wait (this wavefront's pieces of that stage may stay in flight) in front of a raw s_barrier - HBM latency is two
-// stages of arithmetic, and there is ONE barrier per stage: with TPS = 2 half as many as the fp32 kernel, whose eight
-// wavefronts meet at every tile and so keep walking its phases (matrix products, soft-max, matrix products) in lock step.
-// Q stays an fp32 row per lane (one load per workgroup).
-template <int TPS>
+// stages of arithmetic, and there is ONE barrier per stage: half as many as the fp32 kernel, whose eight wavefronts meet at
+// every tile and so keep walking its phases (matrix products, soft-max, matrix products) in lock step.  (32-key stages
+// measured the same: profiles/r05.)  Q stays an fp32 row per lane (one load per workgroup).
 struct KvpGeo {
+  static constexpr int TPS = 2;                               // 32-key tiles per stage
   static constexpr int STAGE = TPS * 2 * ptkv::TILE_BYTES;   // per tile: K tile, V tile
   static constexpr size_t LDS = 3 * (size_t)STAGE;
 };
-template <int TPS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD_WAVES, PT_ATTN_FWD_WAVES))) void attn_fwd_kvp_f16x2_kernel(
     const float *__restrict__ qkv, const char *__restrict__ kvp, const float *__restrict__ kv_inv, int kv_nt,
     const int64_t *__restrict__ seq, int L, int H, float p_drop, uint64_t seed, uint32_t stream_id, float *__restrict__ out,
     float *__restrict__ lse, uint32_t *__restrict__ keep_bits) {
-  constexpr int DK = 64, KS = DK / 16, NT = DK / 32, STAGE = KvpGeo<TPS>::STAGE;
+  constexpr int DK = 64, KS = DK / 16, NT = DK / 32, TPS = KvpGeo::TPS, STAGE = KvpGeo::STAGE;
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
   __shared__ __attribute__((aligned(16))) float sBias[2][TPS][TR];
   __shared__ __attribute__((aligned(16))) float sInvK[2][TPS][8], sInvV[2][TPS][8];
@@ -648,7 +647,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
   if (nstages > 1) {
     issue(1, 1);
     // stage 0 is in; the pieces of stage 1 (2 per tile it holds) may stay in flight
-    if (TPS == 1 || ntiles >= 2 * TPS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TPS) : "memory");
+    if (ntiles >= 2 * TPS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TPS) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -748,7 +747,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
     // landed; behind the barrier everybody is done with this buffer.
     if (more) publish(cur ^ 1);
     if (more2) issue(st + 2, nbuf2);
-    if (more2 && (TPS == 1 || (st + 3) * TPS <= ntiles)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TPS) : "memory");
+    if (more2 && (st + 3) * TPS <= ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TPS) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1699,13 +1698,8 @@ __global__ __launch_bounds__(256) void attn_bwd_split_reduce_kernel(const float 
 }
 
 template <typename K>
-static int set_lds(K kernel, int parts) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(parts * ATTN_LDS));
-  if (e != hipSuccess) {
-    g_pt_last_hip_error = e;
-    return PTAMD_ERR_HIP;
-  }
+static int set_lds(K kernel, size_t bytes) {  // idempotent, host-only: no state kept between calls
+  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return PTAMD_OK;
 }
 }  // namespace ptattn16
@@ -1719,29 +1713,71 @@ namespace {
 // the CUs, 8 wavefronts as 4 groups x 2 halves of the streamed dimension (128 per workgroup; W4 = 4 plain wavefronts for
 // the dK/dV kernel, below); when even 128 per workgroup would, 4 wavefronts as 2 groups x 2 halves (64 per workgroup)
 enum Shape { W8 = 0, W4 = 1, W4_HALVES = 2, W8_HALVES = 3 };
-inline Shape launch_shape(int B, int L, int H) {
-  const size_t cus = (size_t)ptgemm::persistent_grid(0), bh = (size_t)H * B;
-  if ((size_t)((L + 255) / 256) * bh * 2 > cus) return W8;
-  return (size_t)((L + 127) / 128) * bh * 2 > cus ? W8_HALVES : W4_HALVES;
-}
 // In between (as many 128-query workgroups as CUs, or up to twice as many CUs): 8 wavefronts as 4 query groups x 2 halves
 // for the forward and dQ kernels - the same number of workgroups as with 4 wavefronts, half the tile loop, two
 // wavefronts per SIMD; the dK/dV kernel keeps 4 wavefronts there (it has no registers left for a second staged tile
 // pair at 8: 256 VGPRs already; built with 11 spilled registers it measured 0.5 % of a step).
 inline Shape dkv_shape(Shape sh) { return sh == W8_HALVES ? W4 : sh; }
 
-// the 2 x 4 forward shape instead of 2 x 2 where the key range has a tile for every quarter (PTAMD_ATTN_FWD_QUARTERS = 0 in the
-// environment, read at every call: never - for A/B measurements)
-inline bool fwd_quarters(int L) {
-  if (const char *e = getenv("PTAMD_ATTN_FWD_QUARTERS")) return e[0] != '0' && L > 3 * TR;
-  return L > 3 * TR;
+// The backward pass of head size 64 is one sweep over the keys that produces dQ, dK and dV together: UNSPLIT (one
+// workgroup per (protein, head)) where those pairs fill more than half of the chip; otherwise SPLIT (round 6) - the per-GPU
+// share of a strongly scaled batch (4 / 8 / 16 proteins x 512: 92 / ~135 / ~205 us of dQ + dK/dV kernels per layer) - a
+// workgroup per (pair, 256-key block), with the query tiles cut into `qs` ranges too where that is needed for about one
+// workgroup per CU.  Head size 32 takes the two-kernel path (dQ kernel, dK/dV kernel).
+// PTAMD_ATTN_FUSED in the environment (read at every call; for tests, which run small batches, and for A/B measurements):
+// 0 = the two-kernel path, 1 = the unsplit sweep, 2 = the split sweep, whatever the batch (head size 64).  The choice changes
+// the summation order of dQ (two-kernel path) / of dK and dV (split ranges), nothing else.
+enum Bwd { BWD_TWO_KERNELS, BWD_SWEEP, BWD_SPLIT };
+// Every kernel choice of one (B, L, H, dk): the forward pass, the backward pass and the workspace and K / V plane queries
+// all read it, so they cannot disagree.
+struct Plan {
+  Shape shape;      // forward and dQ kernels: W8, W8_HALVES or W4_HALVES (dkv_shape: the dK/dV kernel)
+  bool quarters;    // forward: 2 query groups x 4 key quarters in place of W4_HALVES
+  Bwd bwd;
+  int nkb, qs;      // split sweep: 256-key blocks, query ranges
+  bool kv_planes;   // the forward and backward kernels read pre-split K / V (kv_format.h)
+};
+inline Plan plan(int B, int L, int H, int dk) {
+  const size_t cus = (size_t)ptgemm::persistent_grid(0), bh = (size_t)H * B;
+  Plan pl;
+  if ((size_t)((L + 255) / 256) * bh * 2 > cus) pl.shape = W8;
+  else pl.shape = (size_t)((L + 127) / 128) * bh * 2 > cus ? W8_HALVES : W4_HALVES;
+  // the 2 x 4 forward shape where the key range has a tile for every quarter
+  pl.quarters = dk == 64 && pl.shape == W4_HALVES && L > 3 * TR;
+  pl.bwd = BWD_TWO_KERNELS;
+  if (dk == 64) {
+    if (const char *e = getenv("PTAMD_ATTN_FUSED")) pl.bwd = e[0] == '1' ? BWD_SWEEP : e[0] == '2' ? BWD_SPLIT : BWD_TWO_KERNELS;
+    else pl.bwd = bh * 2 > cus ? BWD_SWEEP : BWD_SPLIT;
+  }
+  pl.nkb = (L + FK - 1) / FK;
+  pl.qs = 1;
+  if (pl.bwd == BWD_SPLIT) {
+    const size_t wg = bh * pl.nkb;
+    const int ntiles = (L + TR - 1) / TR;
+    int qs = 1;
+    while ((size_t)(2 * qs) * wg <= cus && 2 * qs <= ntiles) qs *= 2;
+    const int per = (ntiles + qs - 1) / qs;
+    pl.qs = (ntiles + per - 1) / per;      // ranges that are not empty
+  }
+  // pre-split K / V are read by the 256-query forward kernel and by the sweep with one workgroup per key block (unsplit, or
+  // split with no query ranges - 16 proteins x 8 heads x 512): head size 64, whole 32-token tiles per protein
+  pl.kv_planes = B > 0 && L > 0 && H > 0 && dk == 64 && (L & 31) == 0 && pl.shape == W8 &&
+                 (pl.bwd == BWD_SWEEP || (pl.bwd == BWD_SPLIT && pl.qs == 1));
+  return pl;
 }
+// floats of the split sweep's slabs behind delta in the workspace
+inline size_t split_floats(int B, int L, int H, const Plan &pl) {
+  if (pl.bwd != BWD_SPLIT) return 0;
+  const size_t T = (size_t)B * L, D = (size_t)H * 64;
+  return (size_t)pl.nkb * T * D + (pl.qs > 1 ? (size_t)pl.qs * T * 2 * D : 0);
+}
+
 template <int DK, int NW, int PARTS>
 int launch_fwd(const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *out,
                float *lse, uint32_t *keep_bits, hipStream_t st) {
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
-  if (int rc = set_lds(attn_fwd_f16x2_kernel<DK, NW, PARTS>, PARTS)) return rc;  // idempotent, host-only: no state kept between calls
+  if (int rc = set_lds(attn_fwd_f16x2_kernel<DK, NW, PARTS>, PARTS * ATTN_LDS)) return rc;
   hipLaunchKernelGGL((attn_fwd_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, L, H, p, seed, sid,
                      out, lse, keep_bits);
   return pt_check_launch();
@@ -1753,11 +1789,7 @@ int launch_fwd_quarters(const float *qkv, const int64_t *seq, int B, int L, int 
                         float *lse, uint32_t *keep_bits, hipStream_t st) {
   constexpr size_t LDS = (size_t)4 * 2 * (2 * Tile2U::ELEMS) * sizeof(unsigned short);
   auto kern = attn_fwd_f16x2_kernel<64, 8, 4, Tile2U>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-  if (e != hipSuccess) {
-    g_pt_last_hip_error = e;
-    return PTAMD_ERR_HIP;
-  }
+  if (int rc = set_lds(kern, LDS)) return rc;
   hipLaunchKernelGGL(kern, dim3((L + 63) / 64, H, B), dim3(512), LDS, st, qkv, seq, L, H, p, seed, sid, out, lse, keep_bits);
   return pt_check_launch();
 }
@@ -1767,7 +1799,7 @@ int launch_dq(const float *qkv, const int64_t *seq, const float *o_fwd, const fl
               hipStream_t st) {
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
-  if (int rc = set_lds(attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>, PARTS)) return rc;
+  if (int rc = set_lds(attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>, PARTS * ATTN_LDS)) return rc;
   hipLaunchKernelGGL((attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, o_fwd, d_o, lse,
                      delta, L, H, p, seed, sid, dqkv, row_scale, row_min);
   return pt_check_launch();
@@ -1779,114 +1811,56 @@ int launch_dkv(const float *qkv, const int64_t *seq, const float *d_o, const flo
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
   if (keep_bits && p > 0.f) {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>, PARTS)) return rc;
+    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>, PARTS * ATTN_LDS)) return rc;
     hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, d_o, lse,
                        delta, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits);
   } else {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>, PARTS)) return rc;
+    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>, PARTS * ATTN_LDS)) return rc;
     hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, d_o, lse,
                        delta, L, H, p, seed, sid, dqkv, row_scale, row_min, nullptr);
   }
   return pt_check_launch();
 }
-template <int TPS>
-int launch_fwd_kvp_t(const float *qkv, const char *kvp, const float *kv_inv, const int64_t *seq, int B, int L, int H, float p,
-                     uint64_t seed, uint32_t sid, float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fwd_kvp_f16x2_kernel<TPS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)KvpGeo<TPS>::LDS);
-  if (e != hipSuccess) {
-    g_pt_last_hip_error = e;
-    return PTAMD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(attn_fwd_kvp_f16x2_kernel<TPS>, dim3((L + 255) / 256, H, B), dim3(512), KvpGeo<TPS>::LDS, st, qkv, kvp, kv_inv,
+int launch_fwd_kvp(const float *qkv, const char *kvp, const float *kv_inv, const int64_t *seq, int B, int L, int H, float p,
+                   uint64_t seed, uint32_t sid, float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
+  if (int rc = set_lds(attn_fwd_kvp_f16x2_kernel, KvpGeo::LDS)) return rc;
+  hipLaunchKernelGGL(attn_fwd_kvp_f16x2_kernel, dim3((L + 255) / 256, H, B), dim3(512), KvpGeo::LDS, st, qkv, kvp, kv_inv,
                      (B * L) / 32, seq, L, H, p, seed, sid, out, lse, keep_bits);
   return pt_check_launch();
 }
-// 64-key stages (one barrier per two tiles); PTAMD_ATTN_KVP_TPS = 1 in the environment (read at every call) selects 32-key
-// stages for A/B measurements - same results either way
-int launch_fwd_kvp(const float *qkv, const char *kvp, const float *kv_inv, const int64_t *seq, int B, int L, int H, float p,
-                   uint64_t seed, uint32_t sid, float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
-  const char *e = getenv("PTAMD_ATTN_KVP_TPS");
-  if (e && e[0] == '1') return launch_fwd_kvp_t<1>(qkv, kvp, kv_inv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  return launch_fwd_kvp_t<2>(qkv, kvp, kv_inv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-}
 template <int DK>
-int fwd_by_shape(Shape sh, const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
-                 float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
-  if (sh == W8) return launch_fwd<DK, 8, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  if (sh == W8_HALVES) return launch_fwd<DK, 8, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  if (DK == 64 && fwd_quarters(L)) return launch_fwd_quarters(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+int fwd_by_plan(const Plan &pl, const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
+                float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
+  if (pl.shape == W8) return launch_fwd<DK, 8, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  if (pl.shape == W8_HALVES) return launch_fwd<DK, 8, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  if (pl.quarters) return launch_fwd_quarters(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
   return launch_fwd<DK, 4, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
 }
-// the fused kernel: dk = 64 and enough (protein, head) pairs that one workgroup each fills more than half of the chip
-// (PTAMD_ATTN_FUSED = 0 / 1 in the environment, read at every call: never / whenever dk = 64 - for tests, which run small
-// batches, and for A/B measurements; the choice changes the summation order of dQ, nothing else)
-// PTAMD_ATTN_FUSED in the environment (read at every call; for tests, which run small batches, and for A/B measurements):
-// 0 = never (the two-kernel path), 1 = the unsplit sweep whatever the batch, 2 = the split sweep whatever the batch.  The
-// choice changes the summation order of dQ (two-kernel path) / of dK and dV (split ranges), nothing else.
-inline bool use_fused(int B, int L, int H, int dk) {   // the UNSPLIT one-sweep kernel: one workgroup per (protein, head)
-  if (dk != 64) return false;
-  if (const char *e = getenv("PTAMD_ATTN_FUSED")) return e[0] == '1';
-  return (size_t)B * H * 2 > (size_t)ptgemm::persistent_grid(0);
-}
-// The split sweep (round 6): head size 64 and too few (protein, head) pairs for one workgroup each to fill the chip - the
-// per-GPU share of a strongly scaled batch (4 / 8 / 16 proteins x 512: 92 / ~135 / ~205 us of dQ + dK/dV kernels per layer).
-// split = 1: a workgroup per (pair, 256-key block); 2: the query tiles cut into `qs` ranges too, so that about one
-// workgroup per CU comes out.
-struct FusedSplit {
-  int split, nkb, qs;
-};
-inline FusedSplit fused_split(int B, int L, int H, int dk) {
-  FusedSplit f = {0, (L + FK - 1) / FK, 1};
-  if (dk != 64) return f;
-  if (const char *e = getenv("PTAMD_ATTN_FUSED")) {
-    if (e[0] != '2') return f;
-  } else if (use_fused(B, L, H, dk)) {
-    return f;
-  }
-  const size_t cus = (size_t)ptgemm::persistent_grid(0), wg = (size_t)B * H * f.nkb;
-  const int ntiles = (L + TR - 1) / TR;
-  int qs = 1;
-  while ((size_t)(2 * qs) * wg <= cus && 2 * qs <= ntiles) qs *= 2;
-  const int per = (ntiles + qs - 1) / qs;
-  f.qs = (ntiles + per - 1) / per;      // ranges that are not empty
-  f.split = f.qs > 1 ? 2 : 1;
-  return f;
-}
-inline size_t fused_split_floats(int B, int L, int H, const FusedSplit &f) {   // slabs behind delta in the workspace
-  if (!f.split) return 0;
-  const size_t T = (size_t)B * L, D = (size_t)H * 64;
-  return (size_t)f.nkb * T * D + (f.split == 2 ? (size_t)f.qs * T * 2 * D : 0);
-}
-int launch_fused_split(const FusedSplit &f, const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o,
+int launch_fused_split(const Plan &pl, const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o,
                        const float *lse, float *delta, float *slabs, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
                        float *dqkv, uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits, const char *kvp,
                        const float *kv_inv, hipStream_t st) {
   const size_t items = (size_t)B * L * H * 16, T = (size_t)B * L;
   const int D = H * 64;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, o_fwd, d_o, B * L, L, H, 64, delta);
-  const bool bits = keep_bits != nullptr && p > 0.f;
-  float *dq_part = slabs, *dkv_part = slabs + (size_t)f.nkb * T * D;
+  const bool bits = keep_bits != nullptr && p > 0.f, ranges = pl.qs > 1;
+  float *dq_part = slabs, *dkv_part = slabs + (size_t)pl.nkb * T * D;
   // (pre-split K / V only where the 256-query forward kernel reads them too: one workgroup per key block, no query ranges)
-  auto kern = f.split == 2 ? (bits ? attn_bwd_fused_f16x2_kernel<true, false, 2> : attn_bwd_fused_f16x2_kernel<false, false, 2>)
-              : kvp        ? (bits ? attn_bwd_fused_f16x2_kernel<true, true, 1> : attn_bwd_fused_f16x2_kernel<false, true, 1>)
-                           : (bits ? attn_bwd_fused_f16x2_kernel<true, false, 1> : attn_bwd_fused_f16x2_kernel<false, false, 1>);
-  if (kvp && f.split == 2) return PTAMD_ERR_BAD_SHAPE;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-  if (e != hipSuccess) {
-    g_pt_last_hip_error = e;
-    return PTAMD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(kern, dim3(f.nkb * f.qs, H, B), dim3(512), FUSED_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv,
-                     row_scale, row_min, keep_bits, kvp, kv_inv, (B * L) / 32, dq_part, dkv_part, f.qs);
+  auto kern = ranges ? (bits ? attn_bwd_fused_f16x2_kernel<true, false, 2> : attn_bwd_fused_f16x2_kernel<false, false, 2>)
+              : kvp  ? (bits ? attn_bwd_fused_f16x2_kernel<true, true, 1> : attn_bwd_fused_f16x2_kernel<false, true, 1>)
+                     : (bits ? attn_bwd_fused_f16x2_kernel<true, false, 1> : attn_bwd_fused_f16x2_kernel<false, false, 1>);
+  if (kvp && ranges) return PTAMD_ERR_BAD_SHAPE;
+  if (int rc = set_lds(kern, FUSED_LDS)) return rc;
+  hipLaunchKernelGGL(kern, dim3(pl.nkb * pl.qs, H, B), dim3(512), FUSED_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv,
+                     row_scale, row_min, keep_bits, kvp, kv_inv, (B * L) / 32, dq_part, dkv_part, pl.qs);
   int rc = pt_check_launch();
   if (rc) return rc;
   const dim3 rgrid((unsigned)((T + 7) / 8));
-  if (f.split == 2)
-    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<true>, rgrid, dim3(256), 0, st, dq_part, f.nkb, dkv_part, f.qs, T, D, dqkv,
+  if (ranges)
+    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<true>, rgrid, dim3(256), 0, st, dq_part, pl.nkb, dkv_part, pl.qs, T, D, dqkv,
                        row_scale, row_min);
   else
-    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<false>, rgrid, dim3(256), 0, st, dq_part, f.nkb, dkv_part, f.qs, T, D, dqkv,
+    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<false>, rgrid, dim3(256), 0, st, dq_part, pl.nkb, dkv_part, pl.qs, T, D, dqkv,
                        row_scale, row_min);
   return pt_check_launch();
 }
@@ -1898,11 +1872,7 @@ int launch_fused(const float *qkv, const int64_t *seq, const float *o_fwd, const
   const bool bits = keep_bits != nullptr && p > 0.f;
   auto kern = kvp ? (bits ? attn_bwd_fused_f16x2_kernel<true, true> : attn_bwd_fused_f16x2_kernel<false, true>)
                   : (bits ? attn_bwd_fused_f16x2_kernel<true, false> : attn_bwd_fused_f16x2_kernel<false, false>);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-  if (e != hipSuccess) {
-    g_pt_last_hip_error = e;
-    return PTAMD_ERR_HIP;
-  }
+  if (int rc = set_lds(kern, FUSED_LDS)) return rc;
   hipLaunchKernelGGL(kern, dim3(1, H, B), dim3(512), FUSED_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv, row_scale,
                      row_min, keep_bits, kvp, kv_inv, (B * L) / 32, (float *)nullptr, (float *)nullptr, 1);
   return pt_check_launch();
@@ -1924,27 +1894,19 @@ int bwd_by_shape(Shape sh, const float *qkv, const int64_t *seq, const float *o_
 }  // namespace
 }  // namespace ptattn16
 
-// pre-split K / V (kv_format.h) are read by the 256-query forward kernel and the one-sweep backward kernel: head size 64, whole
-// 32-token tiles per protein, and the batch shapes at which exactly those two kernels run
-bool pt_attention_f16x2_reads_kv_planes(int B, int L, int H, int dk) {
-  using namespace ptattn16;
-  // (round 6: also the split sweep with one workgroup per key block - 16 proteins x 8 heads x 512 - whose forward pass is the
-  // 256-query kernel as well)
-  if (!(B > 0 && L > 0 && H > 0 && dk == 64 && (L & 31) == 0 && launch_shape(B, L, H) == W8)) return false;
-  return use_fused(B, L, H, dk) || fused_split(B, L, H, dk).split == 1;
-}
+bool pt_attention_f16x2_reads_kv_planes(int B, int L, int H, int dk) { return ptattn16::plan(B, L, H, dk).kv_planes; }
 
 int pt_attention_fwd_f16x2(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float p, uint64_t seed,
                            uint32_t sid, float *out, float *lse, uint32_t *keep_bits, const void *kv_planes, const float *kv_inv,
                            hipStream_t st) {
   using namespace ptattn16;
+  const Plan pl = plan(B, L, H, dk);
   if (kv_planes) {
-    if (!kv_inv || !pt_attention_f16x2_reads_kv_planes(B, L, H, dk)) return PTAMD_ERR_BAD_SHAPE;
+    if (!kv_inv || !pl.kv_planes) return PTAMD_ERR_BAD_SHAPE;
     return launch_fwd_kvp(qkv, static_cast<const char *>(kv_planes), kv_inv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
   }
-  const Shape sh = launch_shape(B, L, H);
-  return dk == 64 ? fwd_by_shape<64>(sh, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st)
-                  : fwd_by_shape<32>(sh, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  return dk == 64 ? fwd_by_plan<64>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st)
+                  : fwd_by_plan<32>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
 }
 
 // (the one-sweep kernel and, on the two-kernel path, the dK / dV kernel - both keep keys in lanes; the dQ kernel draws them)
@@ -1954,7 +1916,7 @@ bool pt_attention_bwd_f16x2_reads_keep_bits(int B, int L, int H, int dk) { retur
 size_t pt_attention_bwd_f16x2_slab_floats(int B, int L, int H, int dk) {
   using namespace ptattn16;
   if (B <= 0 || L <= 0 || H <= 0) return 0;
-  return fused_split_floats(B, L, H, fused_split(B, L, H, dk));
+  return split_floats(B, L, H, plan(B, L, H, dk));
 }
 
 int pt_attention_bwd_f16x2(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
@@ -1962,18 +1924,17 @@ int pt_attention_bwd_f16x2(const float *qkv, const int64_t *seq, const float *o_
                            uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits, const void *kv_planes,
                            const float *kv_inv, float *slabs, size_t slab_floats, hipStream_t st) {
   using namespace ptattn16;
-  if (kv_planes && (!kv_inv || !pt_attention_f16x2_reads_kv_planes(B, L, H, dk))) return PTAMD_ERR_BAD_SHAPE;
+  const Plan pl = plan(B, L, H, dk);
+  if (kv_planes && (!kv_inv || !pl.kv_planes)) return PTAMD_ERR_BAD_SHAPE;
   // (the forward kernel's decisions are read by the fused kernel and by the dK / dV kernel of the two-kernel path)
-  if (use_fused(B, L, H, dk))
+  if (pl.bwd == BWD_SWEEP)
     return launch_fused(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
                         static_cast<const char *>(kv_planes), kv_inv, st);
-  const FusedSplit fs = fused_split(B, L, H, dk);
-  if (fs.split) {
-    if (!slabs || slab_floats < fused_split_floats(B, L, H, fs)) return PTAMD_ERR_WORKSPACE;
-    return launch_fused_split(fs, qkv, seq, o_fwd, d_o, lse, delta, slabs, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
+  if (pl.bwd == BWD_SPLIT) {
+    if (!slabs || slab_floats < split_floats(B, L, H, pl)) return PTAMD_ERR_WORKSPACE;
+    return launch_fused_split(pl, qkv, seq, o_fwd, d_o, lse, delta, slabs, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
                               static_cast<const char *>(kv_planes), kv_inv, st);
   }
-  const Shape sh = launch_shape(B, L, H);
-  return dk == 64 ? bwd_by_shape<64>(sh, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st)
-                  : bwd_by_shape<32>(sh, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
+  return dk == 64 ? bwd_by_shape<64>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st)
+                  : bwd_by_shape<32>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
 }

@@ -254,17 +254,15 @@ int launch_hp_g(const HpParams &p, int splits, hipStream_t st) {
 // slower and at the 256-VGPR limit; 128 x 128 tiles (HpGeom<2, 2, 2, true>) 30-50 % slower.
 typedef HpGeom<4, 2, 2, true> Geom;
 
-template <int EPI>
+template <int EPI, bool KVP = false>
 int launch_hp3(const HpParams &p, int splits, hipStream_t st);
-// the three-stage kernel (below) wherever the float4 epilogue applies; PTAMD_HP_STAGES=2 in the environment (read at every
-// call) selects the two-buffer kernel for A/B measurements
+// the three-stage kernel (below) wherever the float4 epilogue applies, the two-buffer kernel elsewhere
 template <int EPI>
 int launch_hp(const HpParams &p, int splits, hipStream_t st) {
-  const char *e = getenv("PTAMD_HP_STAGES");
   // (the no-dropout epilogue instantiation of the three-stage kernel spills 45 registers - its epilogue has no generator
   // loop to keep the two 32-row blocks apart - so those launches take the full instantiation, whose dropout branch is a
   // run-time no-op at p = 0: same results, no spills)
-  if (p.g.vec_epilogue && !(e && e[0] == '2')) return launch_hp3<EPI == ptgemm::EPI_NODROP ? ptgemm::EPI_FULL : EPI>(p, splits, st);
+  if (p.g.vec_epilogue) return launch_hp3<EPI == ptgemm::EPI_NODROP ? ptgemm::EPI_FULL : EPI>(p, splits, st);
   if (p.g.gate_mask_out) return PTAMD_ERR_BAD_SHAPE;   // only the three-stage kernel's epilogue writes the 1-bit gate
   return launch_hp_g<Geom, EPI>(p, splits, st);
 }
@@ -284,21 +282,17 @@ int launch_hp(const HpParams &p, int splits, hipStream_t st) {
 //     also waited for the fragment reads in flight;
 //   * the sixteen fragment reads of a stage are issued in one burst behind the barrier (inline asm, counted lgkmcnt): the
 //     first twelve MFMAs start when the first eight have returned.
-// Two geometries: WM = 4 - eight wavefronts, 256 x 128 tile, three stage buffers, one workgroup per CU (160 KiB); WM = 2 - four
-// wavefronts, 128 x 128 tile, two stage buffers, TWO workgroups per CU (72 KiB each): the tile epilogue of one workgroup (LDS
-// transposes, dropout generator, gate / residual reads, the tile's stores) runs beside the main loop of the other instead
-// of leaving the matrix pipe idle - for the K = 512 products, whose epilogue is a third of a tile's time.
-template <int WM_>
-struct Hp3G {
-  static constexpr int WM = WM_, NW = 2 * WM, THREADS = 64 * NW, TILE_M = 64 * WM, BK = 32, NSTAGE = WM == 4 ? 3 : 2;
-  static constexpr int A_BLOCKS = 2 * WM, B_BLOCKS = 4, PER_WAVE = (A_BLOCKS + B_BLOCKS) * 4 / NW;   // 6 or 8 pieces of 1 KiB
+// The 128-row geometry (four wavefronts, two stage buffers, two workgroups per CU so that one's epilogue runs beside the
+// other's main loop) measured the same per product and +0.1 ms in the step (profiles/r04/NOTES.md section 4): at the package
+// power cap a better overlap buys nothing, only less energy per tile does.
+struct Hp3 {
+  static constexpr int WM = 4, NW = 2 * WM, THREADS = 64 * NW, TILE_M = 64 * WM, BK = 32, NSTAGE = 3;
+  static constexpr int A_BLOCKS = 2 * WM, B_BLOCKS = 4, PER_WAVE = (A_BLOCKS + B_BLOCKS) * 4 / NW;   // 6 pieces of 1 KiB
   static constexpr int RB_BYTES = 4096, A_STAGE = A_BLOCKS * RB_BYTES, STAGE_BYTES = (A_BLOCKS + B_BLOCKS) * RB_BYTES;
   static constexpr int SCRATCH_BYTES = NW * 2048;
   static constexpr size_t LDS = (size_t)NSTAGE * STAGE_BYTES + SCRATCH_BYTES;
-  static constexpr int WG_PER_CU = WM == 4 ? 1 : 2;
-  static_assert(LDS * WG_PER_CU <= 160 * 1024, "the LDS of a CU");
+  static_assert(LDS <= 160 * 1024, "the LDS of a CU");
 };
-typedef Hp3G<4> Hp3;
 
 // the epilogue of one wavefront's 64 x 64 block (TI = 2), eight rows at a time through `scratch` (512 floats): bias / ReLU /
 // dropout in the MFMA layout, residual / gate / accumulate operands and the stores as float4 rows.  Arithmetic, order of
@@ -465,9 +459,9 @@ __device__ __forceinline__ void hp3_epilogue(const GemmParams &p, const f32x16 (
 
 #define PT_DS_READ_B128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
-template <int EPI, int WM, bool KVP = false>
-__global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const HpParams p) {
-  using G = Hp3G<WM>;
+template <int EPI, bool KVP = false>
+__global__ __launch_bounds__(Hp3::THREADS, 2) void gemm_hp3_kernel(const HpParams p) {
+  using G = Hp3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *const scratch = reinterpret_cast<float *>(smem + G::NSTAGE * G::STAGE_BYTES);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -496,17 +490,15 @@ __global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const Hp
     return false;
   };
   // piece i of this wavefront: q = wave + NW i of the stage = block row q >> 2 (A first, then the 4 of B), (k block, plane) =
-  // q & 3 = wave & 3.  Eight wavefronts: pieces 0..3 are A block rows 2 i + (wave >> 2), pieces 4, 5 B block rows 2 (i - 4) +
-  // (wave >> 2); four wavefronts: pieces 0..3 A block rows i, pieces 4..7 B block rows i - 4.
-  constexpr int RSTEP = G::NW / 4;                          // block rows between consecutive pieces of a wavefront
+  // q & 3 = wave & 3: pieces 0..3 are A block rows 2 i + (wave >> 2), pieces 4, 5 B block rows 2 (i - 4) + (wave >> 2).
   const int rb_in_tile = wave >> 2, rest_bytes = (wave & 3) * 1024;
   const char *const a_base = p.a_planes + rest_bytes + lane * 16, *const b_base = p.b_planes + rest_bytes + lane * 16;
   const int64_t row_bytes = (int64_t)p.kb16 * 2048;     // bytes of one block row of an operand: KB16 blocks x 2 planes x 1 KiB
   auto issue_piece = [&](const Cursor &c, int buf, int i) __attribute__((always_inline)) {
     const int q = wave + G::NW * i;
     const bool is_b = i >= 4;                                // (compile-time per call site)
-    const int rb = is_b ? min((c.it.bn0 >> 5) + RSTEP * (i - 4) + rb_in_tile, p.b_rb_last)
-                        : min((c.it.bm0 >> 5) + RSTEP * i + rb_in_tile, p.a_rb_last);
+    const int rb = is_b ? min((c.it.bn0 >> 5) + 2 * (i - 4) + rb_in_tile, p.b_rb_last)
+                        : min((c.it.bm0 >> 5) + 2 * i + rb_in_tile, p.a_rb_last);
     const char *g = (is_b ? b_base : a_base) + (int64_t)rb * row_bytes + (int64_t)(c.k0 >> 4) * 2048;
     dma16(g, smem + buf * G::STAGE_BYTES + q * 1024);
   };
@@ -536,7 +528,7 @@ __global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const Hp
   for (int i = 0; i < G::PER_WAVE; ++i) issue_piece(ld, 0, i);
   bool more_loads = advance(ld);
   int ahead = 1;                 // stages issued and not yet waited for (this one included)
-  if (G::NSTAGE == 3 && more_loads) {
+  if (more_loads) {
 #pragma unroll
     for (int i = 0; i < G::PER_WAVE; ++i) issue_piece(ld, 1, i);
     more_loads = advance(ld);
@@ -549,13 +541,13 @@ __global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const Hp
     // order among themselves, so "at most 6 outstanding" implies the older six pieces are in - the tile stores of an
     // epilogue that may still be in the queue only make the wait conservative, never wrong.)
     if (landed > 0) --landed;
-    else if (G::NSTAGE == 3 && ahead >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else if (ahead >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // ... and everybody's; everybody is done with the buffer that is refilled below
     __builtin_amdgcn_sched_barrier(0);
     const uint32_t va = va0 + (uint32_t)buf * G::STAGE_BYTES, vb = vb0 + (uint32_t)buf * G::STAGE_BYTES;
-    // the buffer the stage issued during this one goes to: (buf + 2) % 3, read last in stage c - 1 - or the other of two
-    const int nbuf = G::NSTAGE == 3 ? (buf >= 1 ? buf - 1 : 2) : buf ^ 1;
+    // the buffer the stage issued during this one goes to: (buf + 2) % 3, read last in stage c - 1
+    const int nbuf = buf >= 1 ? buf - 1 : 2;
     f16x8 fa[2][2][2], fb[2][2][2];            // [k block][tile][plane]
     PT_DS_READ_B128(fa[0][0][0], va, 0);
     PT_DS_READ_B128(fa[0][0][1], va, 1024);
@@ -588,10 +580,7 @@ __global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const Hp
           for (int j = 0; j < 2; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kb][i][ta], fb[kb][j][tb], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (issue) {
-          issue_piece(ld, nbuf, kb * 3 + pr);
-          if (G::PER_WAVE == 8 && pr == 2) issue_piece(ld, nbuf, 6 + kb);   // eight pieces in six slots
-        }
+        if (issue) issue_piece(ld, nbuf, kb * 3 + pr);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -632,24 +621,14 @@ __global__ __launch_bounds__(Hp3G<WM>::THREADS, 2) void gemm_hp3_kernel(const Hp
   }
 }
 
-template <int EPI, int WM, bool KVP = false>
-int launch_hp3_g(const HpParams &p, int splits, hipStream_t st) {
-  using G = Hp3G<WM>;
-  const int work = ((p.g.M + G::TILE_M - 1) / G::TILE_M) * ((p.g.N + HBN - 1) / HBN) * splits;
-  auto kern = gemm_hp3_kernel<EPI, WM, KVP>;
-  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
-  const int slots = ptgemm::persistent_grid(p.g.reserved_cus) * G::WG_PER_CU;
-  hipLaunchKernelGGL(kern, dim3(work < slots ? work : slots), dim3(G::THREADS), G::LDS, st, p);
-  return pt_check_launch();
-}
-// The 256-row geometry is the one in use.  The 128-row one (two workgroups per CU, so that one's epilogue runs beside the
-// other's main loop) measured the SAME per product (QKV 99.8 against 102.5 us, FFN-1 139 against 137, gated dX 146 against
-// 147) and +0.1 ms in the step (profiles/r04/NOTES.md section 4): at the package power cap a better overlap buys nothing, only
-// less energy per tile does.  PTAMD_HP_TILE = 128 in the environment (read at every call) selects it for measurements.
-template <int EPI>
+template <int EPI, bool KVP>
 int launch_hp3(const HpParams &p, int splits, hipStream_t st) {
-  const char *e = getenv("PTAMD_HP_TILE");
-  return (e && e[0] == '1') ? launch_hp3_g<EPI, 2>(p, splits, st) : launch_hp3_g<EPI, 4>(p, splits, st);
+  const int work = ((p.g.M + Hp3::TILE_M - 1) / Hp3::TILE_M) * ((p.g.N + HBN - 1) / HBN) * splits;
+  auto kern = gemm_hp3_kernel<EPI, KVP>;
+  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Hp3::LDS));
+  const int slots = ptgemm::persistent_grid(p.g.reserved_cus);   // one workgroup per CU
+  hipLaunchKernelGGL(kern, dim3(work < slots ? work : slots), dim3(Hp3::THREADS), Hp3::LDS, st, p);
+  return pt_check_launch();
 }
 
 // ---------------------------------------------------------------------------------------------- writers of the format
@@ -952,7 +931,7 @@ int ptamd_gemm_hp(const ptamd_gemm_hp_args *a, void *stream) {
         a->gate_mask_out || a->dropout_p != 0.f || a->flags != 0)
       return PTAMD_ERR_BAD_SHAPE;
     if (!pt_aligned16(a->kv_planes)) return PTAMD_ERR_ALIGN;
-    return launch_hp3_g<ptgemm::EPI_FULL, 4, true>(p, 1, st);
+    return launch_hp3<ptgemm::EPI_FULL, true>(p, 1, st);
   }
   const bool plain = !a->bias && !a->residual && !a->gate_mask && !a->gate_mask_out &&
                      !(a->flags & (PTAMD_EPI_RELU | PTAMD_EPI_TANH | PTAMD_EPI_ACCUM)) && a->dropout_p == 0.f;

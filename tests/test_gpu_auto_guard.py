@@ -382,7 +382,7 @@ def test_stored_decisions_are_bit_identical(dev):
     import os
     res = {}
     old = os.environ.get("PTAMD_ATTN_FUSED")
-    os.environ["PTAMD_ATTN_FUSED"] = "1"          # (8 proteins x 8 heads would take the two-kernel path)
+    os.environ["PTAMD_ATTN_FUSED"] = "1"          # (8 proteins x 8 heads would take the split sweep)
     try:
         for flags in ((True, True), (False, False), (True, False), (False, True)):
             model, batch = _setup(dev, 2, 8, 512, 2048, [512] * 8, seed=37, dropout=0.1)
