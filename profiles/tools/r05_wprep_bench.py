@@ -18,7 +18,6 @@ am = synthetic.angle_means(synthetic.make_batch([64], seed=1)["true_ang"])
 m = EncoderOnlyTransformer(6, 8, 512, 2048, 512, VOCAB, am, True, dropout=0.1).to(dev).train()
 flat, grad = m.flat_parameters()
 grad.normal_(0, 1e-3)
-m.__dict__["_fwd_grad"] = True
 sq = torch.ones(1, device=dev)
 
 
@@ -36,19 +35,19 @@ def timeit(fn, reps=100):
 
 
 m.weights_prep = False
-m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True)
+m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True)
 cache = next(iter(m.__dict__["_scale_caches"].values()))
 prep = cache["prep"]
 
 
 def old_path():
     K.sgd_step(flat, grad, sq, 1.0, 0.0, 0.0)
-    m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True)
+    m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True)
 
 
 print("sgd_step alone                                   %7.1f us" % timeit(lambda: K.sgd_step(flat, grad, sq, 1.0, 0.0, 0.0)))
 print("sgd_step + scales + bounds + split_rows + _cols  %7.1f us" % timeit(old_path))
-print("scales + bounds + split_rows + _cols             %7.1f us" % timeit(lambda: m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True)))
+print("scales + bounds + split_rows + _cols             %7.1f us" % timeit(lambda: m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True)))
 print("ptamd_weights_prep (no update, planes)           %7.1f us" % timeit(lambda: prep.prepare(flat, with_planes=True)))
 print("ptamd_weights_prep (no update, no planes)        %7.1f us" % timeit(lambda: prep.prepare(flat, with_planes=False)))
 print("ptamd_sgd_step_prep (planes)                     %7.1f us" % timeit(lambda: prep.sgd_step(flat, grad, sq, 1.0, 0.0, 0.0, with_planes=True)))

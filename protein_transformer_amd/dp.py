@@ -229,7 +229,10 @@ def all_reduce_gradients(model, empty=False):
     the step (its gradient buffer is zero and no backward ran): it issues the same reductions, in the same order."""
     if world_size() == 1:
         return
-    model.__dict__["_grad_dirty"] = True     # (a rank with an empty shard ran no backward pass, yet its buffer receives the sum)
+    # the reduction writes the gradient buffer through a raw pointer (a rank with an empty shard ran no backward pass, yet
+    # its buffer receives the sum); duck-typed models without `grads_written` keep no stamp of that buffer
+    if getattr(model, "grads_written", None) is not None:
+        model.grads_written()
     meter = COMM_METER is not None and torch.cuda.is_available()
     if meter:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -305,9 +305,6 @@ def linear_bwd_weight(dy, x, dw, dbias=None, arith=None, dy_scale=None, x_scale=
                 b_kmajor=True, flags=EPI_ACCUM, split_k=pick_split_k(N, K, T), colsum=dbias, arith=arith)
 
 
-GROUP_DW = True          # the weight-gradient products of a layer in one launch where they qualify (knob for A/B and tests)
-
-
 GROUP_MIN_K = int(os.environ.get("PTAMD_GROUP_MIN_K", 1024))      # fewest tokens per item of a group (knob for measurements)
 
 

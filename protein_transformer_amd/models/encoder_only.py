@@ -18,8 +18,8 @@ Reference quirks reproduced on purpose: the embedding is added t
 (Attention.py:31), there is no final LayerNorm, pad id 20 has an ordinary embedding row, and the
 output layer starts as weight 0 / bias arctanh(angle_means) (encoder_only.py:28-34).
 """
+import collections
 import math
-import os
 
 import numpy as np
 import torch
@@ -459,6 +459,14 @@ class _TransformerBase(nn.Module):
         the first epoch ran on the scales / bounds / planes of the weights of the FIRST validation.)"""
         self.__dict__["_weights_generation"] = self.__dict__.get("_weights_generation", 0) + 1
 
+    def grads_written(self):
+        """The flat gradient buffer was written through a raw pointer (the backward pass, a collective): moves `grads_stamp`."""
+        self.__dict__["_grads_generation"] = self.__dict__.get("_grads_generation", 0) + 1
+
+    def grads_stamp(self):
+        """Moves whenever the flat gradient buffer is replaced or written: by a torch op or through `grads_written`."""
+        return self._flat_grad.data_ptr(), self._flat_grad._version, self.__dict__.get("_grads_generation", 0)
+
     def _forget_prepared_weights(self):
         for c in self.__dict__.get("_scale_caches", {}).values():
             c.pop("fresh", None)
@@ -492,7 +500,8 @@ class _TransformerBase(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     def flat_parameters(self):
-        """(flat parameter buffer, flat gradient buffer): what the fused optimizer / all-reduce operate on."""
+        """(flat parameter buffer, flat gradient buffer): what the fused optimizer / all-reduce operate on.  Whoever writes the
+        gradient buffer through a raw pointer calls `grads_written()` (no torch version counter sees it: `grads_stamp`)."""
         return self._ensure_flat()
 
     def zero_grad(self, set_to_none=False):
@@ -501,30 +510,32 @@ class _TransformerBase(nn.Module):
         else:
             super().zero_grad(set_to_none=set_to_none)
 
+    def _span(self, first, last):
+        """(offset, numel) of the parameters `first` .. `last` in the flat buffers."""
+        o0, _ = self._layout[first]
+        o1, s1 = self._layout[last]
+        return o0, o1 + int(np.prod(s1)) - o0
+
     def grad_slices(self):
         """(offset, numel) of the flat-gradient slices in the order `_EncoderFn.backward` reports them final (the
         order of the overlapped data-parallel reduction; a rank with an empty shard walks the same list, dp.py)."""
-        def span(first, last):
-            o0, _ = self._layout[first]
-            o1, s1 = self._layout[last]
-            return o0, o1 + int(np.prod(s1)) - o0
-        out = [span("output_projection.weight", "output_projection.bias")]
+        out = [self._span("output_projection.weight", "output_projection.bias")]
         for i in reversed(range(self.nlayers)):
             b = f"encoder.enc_layers.{i}."
-            out.append(span(b + "self_attn.wq.weight", b + "sublayer_connections.1.norm.bias"))
+            out.append(self._span(b + "self_attn.wq.weight", b + "sublayer_connections.1.norm.bias"))
         n_conv = len(self.conv_shapes or [])
         if n_conv:
-            out.append(span("encoder.conv_layers.0.weight", f"encoder.conv_layers.{n_conv - 1}.bias"))
+            out.append(self._span("encoder.conv_layers.0.weight", f"encoder.conv_layers.{n_conv - 1}.bias"))
         if self.use_embedding:
-            out.append(span("encoder.input_embedding.emb.weight", "encoder.input_embedding.emb.weight"))
+            out.append(self._span("encoder.input_embedding.emb.weight", "encoder.input_embedding.emb.weight"))
         return out
 
     # ------------------------------------------------------------------ f16x2 bookkeeping (csrc/scales.hip)
-    def _step_scales(self, flat, arith, p, pa, hp=True):
+    def _step_scales(self, flat, arith, p, pa, hp=True, backward=True):
         """Row / column scales of every encoder weight matrix and the weight-derived bounds of the attention output, the
         FFN hidden layer and its gradient - computed on the device in three small launches per forward pass, so that no
         GEMM of the step has to run a pass over its operands for them.  Returns a list of per-layer dicts (or None when the
-        arithmetic of this pass has no use for them)."""
+        arithmetic of this pass has no use for them).  `backward`: a backward pass follows (default: prepare all it reads)."""
         D, F = self.dlayer, self.dff
         if arith not in (K.GEMM_AUTO, K.GEMM_F16X2) or D > 1024 or self.nlayers == 0:
             return None
@@ -627,7 +638,7 @@ class _TransformerBase(nn.Module):
                 cache["prep"].prepare(self._flat, with_planes=need_planes)
                 cache["fresh"] = (stamp, need_planes)
                 self.__dict__["_prep_launches"] = self.__dict__.get("_prep_launches", 0) + 1
-            if self.training and self.__dict__.get("_fwd_grad", False):
+            if self.training and backward:
                 self.__dict__["_train_cache"] = (cache, need_planes)
             return cache["layers"]
         K.weight_scales(cache["wjobs"])
@@ -638,7 +649,7 @@ class _TransformerBase(nn.Module):
                 K.hp_split_rows(cache["hp_mats"], cache["hp_outs"])
             else:
                 K.hp_split_rows(cache["hp_mats"][0::2], cache["hp_outs"][0::2])
-            if self.hp_dx and F % 32 == 0 and self.__dict__.get("_fwd_grad", False):
+            if self.hp_dx and F % 32 == 0 and backward:
                 K.hp_split_cols(cache["hpT_mats"], cache["hpT_scales"], cache["hpT_outs"])
         return cache["layers"]
 
@@ -724,9 +735,8 @@ class _TransformerBase(nn.Module):
         seed = (self.dropout_seed + 0x9E3779B97F4A7C15 * self._step_counter) & (2 ** 63 - 1)
         # the flat buffer is a leaf of the autograd graph only so that backward() reaches _EncoderFn.backward;
         # gradients are written into the flat gradient buffer directly
-        anchor = flat.detach().requires_grad_(torch.is_grad_enabled())
-        self.__dict__["_fwd_grad"] = torch.is_grad_enabled()      # (grad mode is off inside autograd.Function.forward)
-        out = _EncoderFn.apply(anchor, seq, self, seed)
+        grad = torch.is_grad_enabled()          # (grad mode is off inside autograd.Function.forward)
+        out = _EncoderFn.apply(flat.detach().requires_grad_(grad), seq, self, seed, grad)
         return out.view(seq.shape[0], seq.shape[1], NUM_PREDICTED_ANGLES * 2)
 
     def predict(self, enc_input):
@@ -738,386 +748,373 @@ class _TransformerBase(nn.Module):
         self.attn_dropout = float(p if attn_p is None else attn_p)
 
 
+class _PassPlan:
+    """Every decision of a forward pass and of the backward pass that may follow it, taken from the model's attributes as
+    they are at the forward pass.  Backward reads no attribute that selects a path: a caller may change those before
+    `loss.backward()`, and the buffers of the forward pass (K / V planes, keep bits, gate masks, planes) fit the old ones."""
+    def __init__(self, m, seq, seed, backward):
+        (B, L), D = seq.shape, m.dlayer
+        self.B, self.L, self.D, self.H, self.backward, self.seed = B, L, D, m.nhead, backward, seed
+        self.p, self.pa = (m.dropout, m.attn_dropout) if m.training else (0.0, 0.0)
+        self.arith = ar = K.get_gemm_mode() if m.gemm_mode is None else int(m.gemm_mode)   # every launch of the pass carries it
+        self.attn_arith = ar if m.attn_mode is None else int(m.attn_mode)   # (they find their f16x2 scales: AUTO stays AUTO)
+        if ar == K.GEMM_AUTO and B * L * D < AUTO_F16X2_MIN_WORK:
+            self.arith = K.GEMM_BF16X3      # launch-bound step: the scale bookkeeping of f16x2 costs more than its products save
+        self.fuse = D <= 1024          # backward: LayerNorm backward + the dropout backward behind it in one kernel
+        # Small batches: the weight-gradient products (independent of the dX chain, 40 % of the backward GEMM time) go to a
+        # side stream; the main stream waits for it before a gradient slice is handed on and at the end of the pass.
+        self.side = None
+        if backward and m.side_stream_dw and D >= 512 and B * L >= SIDE_STREAM_MIN_TOKENS and B * L * D <= SIDE_STREAM_MAX_WORK:
+            if m.__dict__.get("_side_stream") is None or m._side_stream.device != seq.device:
+                m.__dict__["_side_stream"] = torch.cuda.Stream(device=seq.device)
+            self.side = m._side_stream
+        # The weight-gradient products of a layer in f16x2 on uniform scales go out in GROUPS (ptamd_gemm_group: one launch
+        # whose items fill the chip in whole rounds with a longer K per item and fewer slabs, one for all split-K reductions).
+        # "pairs": the FFN pair, then the attention pair at the end of the layer (where a pair fills a round: 10.39 against
+        # 10.57 ms at 32 x 512, the layer as one group 10.63); "layer": all four at the end (few tokens, launch-bound: config 3
+        # 7.31 / 7.44 / 7.65 ms as layer / pairs / one by one); "auto" picks by the size of the FFN pair; "off": one by one.
+        self.dw_group = m.dw_group
+        if self.dw_group == "auto":
+            ffn_tiles = -(-D // 256) * -(-m.dff // 128) + -(-m.dff // 256) * -(-D // 128)      # 256 x 128 tiles of dW2 and dW1
+            self.dw_group = "pairs" if ffn_tiles * B * L >= 256 * 2048 else "layer"
+
+    def take_scales(self, m, flat):
+        """The f16x2 scales of the pass and what follows from them (after the front end: its launches come first)."""
+        B, L, D, H, attn = self.B, self.L, self.D, self.H, self.attn_arith
+        # (below HP_MIN_TOKENS the staging GEMM with 128-row tiles is the faster of the two: profiles/r03/r03_tile_height.txt)
+        want_hp = B * L >= HP_MIN_TOKENS and bool(m.hp_forward)
+        scales = self.scales = m._step_scales(flat, self.arith, self.p, self.pa, hp=want_hp, backward=self.backward)
+        # QKV and FFN layer 1 on ptamd_gemm_hp: the LayerNorm kernels write their outputs a second time as pre-split planes
+        self.use_hp = want_hp and scales is not None and "hp_1" in scales[0]
+        self.hp_qkv = self.use_hp and m.hp_qkv
+        # K and V leave the QKV product as the pre-split planes the attention kernels of this shape read (no fp32 K / V)
+        self.kv_planes = self.hp_qkv and m.kv_planes and K.attention_reads_kv_planes(B, L, H, D // H, attn)
+        # the attention dropout decisions, kept for the backward kernel that reads them instead of drawing them again
+        self.keep_bits = self.pa > 0.0 and m.keep_attn_bits and self.backward and K.attention_bwd_reads_keep_bits(B, L, H, D // H, attn)
+        # FFN layer 1 on ptamd_gemm_hp leaves "f1 > 0" as one bit per element for the gated dX product of layer 2
+        self.gate_mask = m.ffn_gate_mask and self.backward
+        # dX of FFN layer 2 on ptamd_gemm_hp: the fused LayerNorm backward that makes dy2 writes it a second time as planes
+        self.hp_dx = self.use_hp and m.hp_dx and self.fuse and "hp_2t" in scales[0] and m.dff % 32 == 0
+        # the f16x2 attention kernels leave the row scales of dqkv and their minimum behind (else: one pass over dqkv)
+        self.attn_row_scales = scales is not None and m.attn_row_scales and K.attention_row_scales_available(D // H, attn)
+        self.top_scales = scales is not None and self.fuse and m.top_layer_scales
+        # the guard of the bound-derived scales: sites whose measured slack is too large do not use their bound (AutoGuard)
+        guard = self.guard = m.auto_guard if (scales is not None and m.auto_guard.enabled) else None
+        self.measure, self.measure_fwd, self.off, self.wide = False, False, None, None
+        if guard is not None:
+            guard.poll()
+            if m.training and self.backward:          # a training step: a backward pass will follow
+                self.measure = guard.want_measure()
+                guard.count_step()
+            else:
+                # no backward pass follows (evaluation, inference): measure the four forward operands in the forward pass -
+                # the first such pass on these weights and every `interval`-th one after it (AutoGuard.want_measure_forward)
+                self.measure_fwd = guard.want_measure_forward()
+                guard.eval_passes += 1
+            self.off, self.wide = guard.off.copy(), guard.wide.copy()
+
+    def prod(self, i, k, **scale_kw):
+        # product k of layer i (AutoGuard.WIDE order): bf16x3 where the weight's scales spread too far along the contraction
+        if self.wide is not None and self.wide[i, k]:
+            return dict(arith=K.GEMM_BF16X3)
+        return dict(arith=self.arith, **scale_kw)
+
+
+_Acts = collections.namedtuple("_Acts", "x mean1 rstd1 h1 qkv att lse x2 mean2 rstd2 h2 f1 kbits fmask kv")   # of one layer
+
+
+def _layer_fwd(plan, m, flat, seq, i, x, hplanes):
+    """Encoder layer i of the forward pass -> (its output, its _Acts)."""
+    Tn, D, H, p, seed, dev = plan.B * plan.L, plan.D, plan.H, plan.p, plan.seed, x.device
+    W = lambda name: m._slice(flat, name)                                      # noqa: E731
+    b = f"encoder.enc_layers.{i}."
+    sid = i * 8
+    sc = plan.scales[i] if plan.scales is not None else None
+    wqkv, bqkv = m._qkv(flat, i)
+    s_h1 = torch.empty(Tn, dtype=torch.int32, device=dev) if sc else None
+    hp_q = plan.hp_qkv and not (plan.wide is not None and plan.wide[i, 0])
+    h1, mean1, rstd1 = K.layernorm_fwd(x, W(b + "sublayer_connections.0.norm.weight"),
+                                       W(b + "sublayer_connections.0.norm.bias"), row_scale=s_h1,
+                                       planes=hplanes if hp_q else None)
+    if isinstance(x, K.PendingRows):          # (the layer below left its output as K slices: made by this LayerNorm)
+        x = x.value
+    kv = None
+    if hp_q and plan.kv_planes:
+        kv = K.attention_kv_buffers(Tn, H, dev)
+        m.__dict__["_kv_plane_passes"] = m.__dict__.get("_kv_plane_passes", 0) + 1
+    if hp_q:
+        qkv = K.gemm_hp(K.hp_view(hplanes, s_h1, Tn, D), sc["hp_qkv"],
+                        torch.empty(Tn, 3 * D, dtype=torch.float32, device=dev), bias=bqkv, kv=kv, kv_col0=D, kv_heads=H)
+    else:
+        qkv = K.linear_fwd(h1, wqkv, bqkv, **plan.prod(i, 0, a_scale=s_h1, b_scale=sc and sc["rs_qkv"]))
+    kbits = None
+    if plan.keep_bits:
+        kbits = K.attention_keep_bits(plan.B, plan.L, H, dev)
+        m.__dict__["_attn_bits_passes"] = m.__dict__.get("_attn_bits_passes", 0) + 1
+    att, lse = K.attention_fwd(qkv, seq, H, plan.pa, seed, sid + _SITE_ATTN, arith=plan.attn_arith, keep_bits=kbits, kv=kv)
+    use_b = sc is not None and not (plan.off is not None and plan.off[i, 0])          # att on its bound (else: exact row scales)
+    x2 = K.linear_fwd(att, W(b + "self_attn.wo.weight"), W(b + "self_attn.wo.bias"), residual=x, ldr=D,
+                      dropout_p=p, seed=seed, stream_id=sid + _SITE_ATTN_OUT,
+                      **plan.prod(i, 1, a_scale=sc["att_scale"] if use_b else None, a_scale_stride=0 if use_b else 1,
+                                  b_scale=sc and sc["rs_o"]))
+    s_h2 = torch.empty(Tn, dtype=torch.int32, device=dev) if sc else None
+    h2, mean2, rstd2 = K.layernorm_fwd(x2, W(b + "sublayer_connections.1.norm.weight"),
+                                       W(b + "sublayer_connections.1.norm.bias"), row_scale=s_h2, planes=hplanes)
+    fmask = None
+    if plan.use_hp and not (plan.wide is not None and plan.wide[i, 2]):
+        if plan.gate_mask:
+            fmask = K.gate_mask_buffer(Tn, m.dff, dev)
+            m.__dict__["_gate_mask_passes"] = m.__dict__.get("_gate_mask_passes", 0) + 1
+        f1 = K.gemm_hp(K.hp_view(hplanes, s_h2, Tn, D), sc["hp_1"],
+                       torch.empty(Tn, m.dff, dtype=torch.float32, device=dev), bias=W(b + "pwff.layer1.bias"),
+                       flags=K.EPI_RELU, dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_HID, gate_mask_out=fmask)
+    else:
+        f1 = K.linear_fwd(h2, W(b + "pwff.layer1.weight"), W(b + "pwff.layer1.bias"), flags=K.EPI_RELU,
+                          dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_HID,
+                          **plan.prod(i, 2, a_scale=s_h2, b_scale=sc and sc["rs_1"]))
+    use_b = sc is not None and not (plan.off is not None and plan.off[i, 1])          # f1 on its bound
+    # (few tokens: the K slices of this product go to the next layer's LayerNorm unreduced - kernels.PendingRows)
+    x3 = K.linear_fwd(f1, W(b + "pwff.layer2.weight"), W(b + "pwff.layer2.bias"), residual=x2, ldr=D,
+                      dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_OUT, defer_reduce=i + 1 < m.nlayers,
+                      **plan.prod(i, 3, a_scale=sc["f1_scale"] if use_b else None, a_scale_stride=0 if use_b else 1,
+                                  b_scale=sc and sc["rs_2"]))
+    if plan.measure_fwd:
+        gs = sc["guard_stats"][i]
+        K.weight_scales([dict(w=t, stats=gs[j], rows_only=True) for j, t in ((0, att), (1, f1), (3, h1), (4, h2))])
+    return x3, _Acts(x, mean1, rstd1, h1, qkv, att, lse, x2, mean2, rstd2, h2, f1, kbits, fmask, kv)
+
+
+class _GradSchedule:
+    """The weight-gradient work of one backward pass: on the plan's side stream or the main one, one by one or in the plan's
+    groups (`later`, `flush`), and the hand-over of each final slice of the flat gradient to `model.grad_hook` (`done`)."""
+    def __init__(self, model, plan, main):
+        self.model, self.side, self.group, self.main = model, plan.side, plan.dw_group, main
+        self.queue = []           # products held back for a group
+        self.ln_pending = []      # deferred (dgamma, dbeta) reductions of the LayerNorm backward kernels: one launch per flush
+        # Operands the side stream reads, allocated on the main stream, are kept ALIVE until the main stream has waited for the
+        # side stream (`join`) instead of `record_stream`: blocks parked behind a side-stream event return to the allocator when
+        # the host notices, and reserved memory crept (9.3 -> 9.9 GiB over 4,000 steps, profiles/r05/r05_soak.txt).
+        self.keep = []
+
+    def run(self, fn, *args, keep=(), **kw):
+        # fn(*args, **kw) on the side stream behind a wait for the main one, if there is one (`keep`: read there, made here)
+        if self.side is None:
+            return fn(*args, **kw)
+        self.side.wait_stream(self.main)
+        self.keep.extend(keep)
+        with torch.cuda.stream(self.side):
+            return fn(*args, **kw)
+
+    def later(self, dy, x, gw, gb, arith=None, dy_scale=None, x_scale=None):
+        if self.group == "off":
+            return self.run(K.linear_bwd_weight, dy, x, gw, gb, keep=(dy, x), arith=arith, dy_scale=dy_scale, x_scale=x_scale)
+        self.queue.append((dy, x, gw, gb, arith, dy_scale, x_scale))
+
+    def flush(self):
+        jobs, self.queue = self.queue, []
+        # members of a group: f16x2 on uniform scales (the top layer's FFN gradients come without - no fused LayerNorm
+        # backward above them - and go one by one, like everything in the other arithmetics)
+        ok = [j for j in jobs if j[5] is not None and j[6] is not None and j[1].shape[1] % 4 == 0]
+        tiles = sum(-(-j[0].shape[1] // 256) * -(-j[1].shape[1] // 128) for j in ok)
+        sk = K.pick_group_split(tiles, ok[0][0].shape[0]) if 2 <= len(ok) <= 4 else 0
+        if sk < 2:
+            ok = []
+        for dy, x, gw, gb, a, sy, sx in jobs:
+            if not any(dy is o[0] and x is o[1] for o in ok):
+                self.run(K.linear_bwd_weight, dy, x, gw, gb, keep=(dy, x), arith=a, dy_scale=sy, x_scale=sx)
+        if ok:
+            group = [(dy, x, gw, gb, sy, sx) for dy, x, gw, gb, a, sy, sx in ok]
+            self.run(K.linear_bwd_weight_group, group, sk, keep=(t for j in ok for t in j[:2]))
+
+    def join(self):
+        if self.side is not None:
+            self.main.wait_stream(self.side)
+            self.keep.clear()                # (whatever is freed from here on is reused behind the side stream's work)
+
+    def done(self, first, last):
+        """The flat-gradient slice of parameters `first` .. `last` is final: hand it to `model.grad_hook`."""
+        hook = self.model.grad_hook
+        if hook is not None:
+            K.layernorm_bwd_flush(self.ln_pending)     # a slice handed to the all-reduce must be final
+            # with a side stream the slice is final once BOTH streams are here: the collective is issued from the side stream
+            # behind a wait for the main one, so the dX chain on the main stream does not stop for the weight-gradient products
+            self.run(hook, *self.model._span(first, last))
+
+
+def _layer_bwd(plan, m, flat, gflat, seq, i, a, carry, dws, s_dqkv_all, dy2_planes):
+    """Encoder layer i of the backward pass.  `carry` (from the layer above, returned for the one below): dx and, made by the
+    fused LayerNorm backward above, dy2 = dropout'(dx) with its row scales, the bound scales of dz1, have_min, have_planes."""
+    dx, dy2, s_dy2, bs_dz1, have_min, have_planes = carry
+    D, H, p, pa, seed, ar, fuse, dev = plan.D, plan.H, plan.p, plan.pa, plan.seed, plan.arith, plan.fuse, dx.device
+    W = lambda name: m._slice(flat, name)                                      # noqa: E731
+    G = lambda name: m._slice(gflat, name)                                     # noqa: E731
+    i32 = lambda: torch.empty(plan.B * plan.L, dtype=torch.int32, device=dev)  # noqa: E731
+    scales, wide = plan.scales, plan.wide
+    b = f"encoder.enc_layers.{i}."
+    sid = i * 8
+    sc = scales[i] if scales is not None else None
+    # x3 = x2 + drop(f1 W2^T + b2)
+    if dy2 is None:
+        dy2 = K.dropout_bwd(dx, p, seed, sid + _SITE_FFN_OUT) if p > 0 else dx
+        if plan.top_scales:
+            # the top layer (no fused LayerNorm backward above it): the uniform scales of dy2 / dz1 from a pass over dy2, so
+            # that its two FFN weight-gradient products run in f16x2 like those of every other layer
+            ts = sc["top_stats"]
+            K.weight_scales([dict(w=dy2, stats=ts, rows_only=True)])
+            K.bound_scales([dict(w=ts, w_index=2, out_scale=sc["dy2_min"]),
+                            dict(ln_gamma=sc["dz1_factor_rec"], sqrt_d=1.0, w=ts, w_index=0, out_scale=sc["dz1_min"])])
+            have_min = True
+    uni = sc is not None and have_min              # uniform scales of both operands: the dW product runs in f16x2
+    o_att, o_f1, o_dz1, o_h1, o_h2 = (bool(v) for v in plan.off[i]) if plan.off is not None else (False,) * 5   # AutoGuard
+    dws.later(dy2, a.f1, G(b + "pwff.layer2.weight"), G(b + "pwff.layer2.bias"), arith=ar,
+              dy_scale=sc["dy2_min"] if uni and not o_f1 else None, x_scale=sc["f1_scale"] if uni and not o_f1 else None)
+    # backward of layer2 and, in its epilogue, of the ReLU + dropout in front of it (gate = saved f1)
+    if dy2_planes is not None and have_planes and not (wide is not None and wide[i, 7]):
+        # dy2 came from the fused LayerNorm backward of the layer above together with its planes: LDS-DMA kernel
+        dz1 = K.gemm_hp(K.hp_view(dy2_planes, s_dy2, plan.B * plan.L, D), sc["hp_2t"],
+                        torch.empty(plan.B * plan.L, m.dff, dtype=torch.float32, device=dev),
+                        residual=a.f1 if a.fmask is None else None, ldr=a.f1.stride(0) if a.fmask is None else 0,
+                        gate_mask=a.fmask, flags=K.EPI_GATE, gate_scale=1.0 / (1.0 - p))
+    else:
+        dz1 = K.linear_bwd_input(dy2, W(b + "pwff.layer2.weight"), gate=a.f1, gate_dropout_p=p, gate_mask=a.fmask,
+                                 **plan.prod(i, 7, a_scale=s_dy2 if sc else None, b_scale=sc and sc["cs_2"]))
+    if plan.measure:     # the true maxima of the five bound-scaled operands of this layer (AutoGuard; every 16th step)
+        gs = sc["guard_stats"][i]
+        K.weight_scales([dict(w=t, stats=gs[j], rows_only=True) for j, t in enumerate((a.att, a.f1, dz1, a.h1, a.h2))])
+    uni1 = uni and not (o_dz1 or o_h2)
+    dws.later(dz1, a.h2, G(b + "pwff.layer1.weight"), G(b + "pwff.layer1.bias"), arith=ar,
+              dy_scale=sc["dz1_min"] if uni1 else None, x_scale=sc["h2_scale"] if uni1 else None)
+    if dws.group != "layer":
+        dws.flush()                                    # the two FFN products now, the two attention products at the end
+    # (few tokens: the K slices of dh2 / dh1 go to the fused LayerNorm backward unreduced - kernels.Slabs)
+    dh2 = K.linear_bwd_input(dz1, W(b + "pwff.layer1.weight"), defer_reduce=fuse,
+                             **plan.prod(i, 6, a_scale=bs_dz1 if sc and not o_dz1 else None, b_scale=sc and sc["cs_1"]))
+    # x2 = x + drop(att Wo^T + bo)
+    g2w, g2b = G(b + "sublayer_connections.1.norm.weight"), G(b + "sublayer_connections.1.norm.bias")
+    if fuse:
+        s_dyo = i32() if sc else None
+        dx2, dyo = K.layernorm_bwd_dropout(dh2, a.x2, W(b + "sublayer_connections.1.norm.weight"), a.mean2, a.rstd2, g2w, g2b,
+                                           dx, p, seed, sid + _SITE_ATTN_OUT, row_scale=s_dyo,
+                                           row_scale_min=sc["dyo_min"] if sc else None, pending=dws.ln_pending)
+    else:
+        s_dyo = None
+        dx2 = K.layernorm_bwd(dh2, a.x2, W(b + "sublayer_connections.1.norm.weight"), a.mean2, a.rstd2, g2w, g2b, dres=dx,
+                              pending=dws.ln_pending)
+        dyo = K.dropout_bwd(dx2, p, seed, sid + _SITE_ATTN_OUT) if p > 0 else dx2
+    uni_o = sc is not None and fuse and not o_att
+    dws.later(dyo, a.att, G(b + "self_attn.wo.weight"), G(b + "self_attn.wo.bias"), arith=ar,
+              dy_scale=sc["dyo_min"] if uni_o else None, x_scale=sc["att_scale"] if uni_o else None)
+    datt = K.linear_bwd_input(dyo, W(b + "self_attn.wo.weight"), **plan.prod(i, 5, a_scale=s_dyo, b_scale=sc and sc["cs_o"]))
+    s_dqkv = s_dqkv_all[i] if plan.attn_row_scales else None
+    dqkv = K.attention_bwd(a.qkv, seq, a.att, datt, a.lse, H, pa, seed, sid + _SITE_ATTN, arith=plan.attn_arith,
+                           row_scale=s_dqkv, row_scale_min=sc["dqkv_min"] if plan.attn_row_scales else None, keep_bits=a.kbits,
+                           kv=a.kv)
+    gw, gb = m._qkv(gflat, i)
+    dq_uni = sc["dqkv_min"] if sc is not None else None
+    if sc is not None and not plan.attn_row_scales:
+        s_dqkv, dq_uni = i32(), sc["dqkv_scale"]
+        K.weight_scales([dict(w=dqkv, row_scale=s_dqkv, stats=sc["dqkv_stats"], rows_only=True)])
+        K.bound_scales([dict(w=sc["dqkv_stats"], w_index=2, out_scale=sc["dqkv_scale"])])
+    uni_h1 = sc is not None and not o_h1
+    dws.later(dqkv, a.h1, gw, gb, arith=ar, dy_scale=dq_uni if uni_h1 else None, x_scale=sc["h1_scale"] if uni_h1 else None)
+    dh1 = K.linear_bwd_input(dqkv, m._qkv(flat, i)[0], defer_reduce=fuse and i > 0,
+                             **plan.prod(i, 4, a_scale=s_dqkv, b_scale=sc and sc["cs_qkv"]))
+    g1w, g1b = G(b + "sublayer_connections.0.norm.weight"), G(b + "sublayer_connections.0.norm.bias")
+    if fuse and i > 0:      # the gradient enters layer i - 1 through ITS FFN-output dropout: made here, with its scales
+        s_dy2, bs_dz1 = (i32(), i32()) if scales is not None else (None, None)
+        below = scales[i - 1] if scales is not None else None
+        dx, dy2 = K.layernorm_bwd_dropout(dh1, a.x, W(b + "sublayer_connections.0.norm.weight"), a.mean1, a.rstd1, g1w, g1b,
+                                          dx2, p, seed, (i - 1) * 8 + _SITE_FFN_OUT, row_scale=s_dy2,
+                                          bound_factor=below["dz1_factor"] if below else None, bound_scale=bs_dz1,
+                                          row_scale_min=below["dy2_min"] if below else None,
+                                          bound_scale_min=below["dz1_min"] if below else None, pending=dws.ln_pending,
+                                          planes=dy2_planes if below else None)
+        have_min = below is not None
+        have_planes = below is not None and dy2_planes is not None
+    else:
+        dx = K.layernorm_bwd(dh1, a.x, W(b + "sublayer_connections.0.norm.weight"), a.mean1, a.rstd1, g1w, g1b, dres=dx2,
+                             pending=dws.ln_pending)
+        dy2 = s_dy2 = bs_dz1 = None
+        have_min = have_planes = False
+    dws.flush()
+    dws.done(b + "self_attn.wq.weight", b + "sublayer_connections.1.norm.bias")
+    return dx, dy2, s_dy2, bs_dz1, have_min, have_planes
+
+
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flat, seq, model, seed):
+    def forward(ctx, flat, seq, model, seed, backward):
+        """`backward`: a backward pass will follow (grad mode is off in here: the caller's `torch.is_grad_enabled()`)."""
         m = model
-        B, L = seq.shape
-        D, H = m.dlayer, m.nhead
-        train = m.training
-        p = m.dropout if train else 0.0
-        pa = m.attn_dropout if train else 0.0
+        plan = _PassPlan(m, seq, seed, backward)
+        B, L, p, ar = plan.B, plan.L, plan.p, plan.arith
         W = lambda name: m._slice(flat, name)                                      # noqa: E731
-        ar = K.get_gemm_mode() if m.gemm_mode is None else int(m.gemm_mode)        # every launch below carries it
-        attn_default = ar                 # the attention kernels find their f16x2 scales themselves: AUTO stays AUTO for them
-        if ar == K.GEMM_AUTO and B * L * D < AUTO_F16X2_MIN_WORK:
-            ar = K.GEMM_BF16X3         # launch-bound step: the scale bookkeeping of f16x2 costs more than its products save
         pe = m.encoder.positional_enc.pe[0]
         # ---- front end: embedding (+ doubled positional add) or one-hot, then the optional Conv1d stack
-        if m.use_embedding:
-            x = K.embed_fwd(seq, W("encoder.input_embedding.emb.weight"), pe, p, seed)
-            cin = m.dmodel
-        else:
-            cin = len(m.vocab)
-            x = K.onehot(seq, cin)
+        x = K.embed_fwd(seq, W("encoder.input_embedding.emb.weight"), pe, p, seed) if m.use_embedding else K.onehot(seq, len(m.vocab))
         conv_saved = []
         for j, (ci, co, k) in enumerate(m.conv_shapes or []):
             y, w2 = K.conv1d_fwd(x, B, L, ci, W(f"encoder.conv_layers.{j}.weight"), W(f"encoder.conv_layers.{j}.bias"), k,
                                    arith=ar)
             conv_saved.append((x, w2))
-            x, cin = y, co
+            x = y
         if not m.use_embedding:
             x = K.posenc_add_fwd(x, pe, B, L, p, seed)             # enc_output += positional_enc(enc_output)
+        plan.take_scales(m, flat)
+        hplanes = torch.empty(K.lib().ptamd_hp_bytes(B * L, plan.D), dtype=torch.uint8, device=x.device) if plan.use_hp else None
         saved = []
-        # f16x2 row scales without passes over the operands: weights and weight-derived bounds once per forward, LayerNorm
-        # outputs from the LayerNorm kernel itself (None: the arithmetic of this pass does not use them)
-        Tn = B * L
-        # (below HP_MIN_TOKENS the staging GEMM with 128-row tiles is the faster of the two: profiles/r03/r03_tile_height.txt)
-        want_hp = Tn >= HP_MIN_TOKENS and bool(m.hp_forward)
-        scales = m._step_scales(flat, ar, p, pa, hp=want_hp)
-        # QKV and FFN layer 1 (the products behind the two LayerNorms) run on ptamd_gemm_hp: the LayerNorm kernel writes its
-        # output a second time as pre-split planes (one buffer, consumed at once), the weights were split above.
-        use_hp = want_hp and scales is not None and "hp_1" in scales[0]
-        hplanes = torch.empty(K.lib().ptamd_hp_bytes(Tn, D), dtype=torch.uint8, device=x.device) if use_hp else None
-        # the guard of the bound-derived scales: sites whose measured slack is too large do not use their bound (AutoGuard)
-        guard = m.auto_guard if (scales is not None and m.auto_guard.enabled) else None
-        measure = False
-        if guard is not None:
-            guard.poll()
-            if train and m.__dict__.get("_fwd_grad", False):          # a training step: a backward pass will follow
-                measure = guard.want_measure()
-                guard.count_step()
-        # a pass that no backward pass follows (evaluation, inference) measures in the forward pass: the four forward operands
-        # (dz1 exists in backward only) - the first such pass on these weights, so that inference does not stay on the
-        # untrusting path, and every `interval`-th one after it (other inputs, same weights: the slack is a property of both)
-        measure_fwd = False
-        if guard is not None and not (train and m.__dict__.get("_fwd_grad", False)):
-            measure_fwd = guard.want_measure_forward()
-            guard.eval_passes += 1
-        off = guard.off if guard is not None else None
-        wide = guard.wide if guard is not None else None
-        ctx_off = None if off is None else (off.copy(), wide.copy())
-
-        def prod(i, k, **scale_kw):
-            """arithmetic + scales of activation x weight product k of layer i (AutoGuard.WIDE order): bf16x3 without scales
-            when the weight's scales spread too far along the contracted index, else the pass's arithmetic with `scale_kw`"""
-            if wide is not None and wide[i, k]:
-                return dict(arith=K.GEMM_BF16X3)
-            return dict(arith=ar, **scale_kw)
         for i in range(m.nlayers):
-            b = f"encoder.enc_layers.{i}."
-            sid = i * 8
-            sc = scales[i] if scales is not None else None
-            wqkv, bqkv = m._qkv(flat, i)
-            s_h1 = torch.empty(Tn, dtype=torch.int32, device=x.device) if sc else None
-            hp_q = use_hp and m.hp_qkv and not (wide is not None and wide[i, 0])
-            h1, mean1, rstd1 = K.layernorm_fwd(x, W(b + "sublayer_connections.0.norm.weight"),
-                                               W(b + "sublayer_connections.0.norm.bias"), row_scale=s_h1,
-                                               planes=hplanes if hp_q else None)
-            if isinstance(x, K.PendingRows):          # (the layer below left its output as K slices: made by this LayerNorm)
-                x = x.value
-            attn_ar_f = attn_default if m.attn_mode is None else m.attn_mode
-            # K and V leave the QKV product as the pre-split planes the attention kernels of this batch shape read (no fp32 K / V at
-            # all: the forward kernel fills its stages by LDS-DMA, the one-sweep backward kernel loads its key rows from them)
-            kv = None
-            if hp_q and m.kv_planes and K.attention_reads_kv_planes(B, L, H, D // H, attn_ar_f):
-                kv = K.attention_kv_buffers(Tn, H, x.device)
-                m.__dict__["_kv_plane_passes"] = m.__dict__.get("_kv_plane_passes", 0) + 1
-            if hp_q:
-                qkv = K.gemm_hp(K.hp_view(hplanes, s_h1, Tn, D), sc["hp_qkv"],
-                                torch.empty(Tn, 3 * D, dtype=torch.float32, device=x.device), bias=bqkv, kv=kv, kv_col0=D, kv_heads=H)
-            else:
-                qkv = K.linear_fwd(h1, wqkv, bqkv, **prod(i, 0, a_scale=s_h1, b_scale=sc and sc["rs_qkv"]))
-            # the dropout decisions of the probabilities, kept for the backward kernel that reads them instead of drawing
-            # them again (8 MB per layer at 32 x 512 x 8 heads; only where that kernel will run)
-            kbits = None
-            if pa > 0.0 and m.keep_attn_bits and m.__dict__.get("_fwd_grad", False) and \
-                    K.attention_bwd_reads_keep_bits(B, L, H, D // H, attn_ar_f):
-                kbits = K.attention_keep_bits(B, L, H, x.device)
-                m.__dict__["_attn_bits_passes"] = m.__dict__.get("_attn_bits_passes", 0) + 1
-            att, lse = K.attention_fwd(qkv, seq, H, pa, seed, sid + _SITE_ATTN, arith=attn_ar_f, keep_bits=kbits, kv=kv)
-            use_b = sc is not None and not (off is not None and off[i, 0])          # att on its bound (else: exact row scales)
-            x2 = K.linear_fwd(att, W(b + "self_attn.wo.weight"), W(b + "self_attn.wo.bias"), residual=x, ldr=D,
-                              dropout_p=p, seed=seed, stream_id=sid + _SITE_ATTN_OUT,
-                              **prod(i, 1, a_scale=sc["att_scale"] if use_b else None, a_scale_stride=0 if use_b else 1,
-                                     b_scale=sc and sc["rs_o"]))
-            s_h2 = torch.empty(Tn, dtype=torch.int32, device=x.device) if sc else None
-            h2, mean2, rstd2 = K.layernorm_fwd(x2, W(b + "sublayer_connections.1.norm.weight"),
-                                               W(b + "sublayer_connections.1.norm.bias"), row_scale=s_h2, planes=hplanes)
-            fmask = None
-            if use_hp and not (wide is not None and wide[i, 2]):
-                # (with a backward pass to come: the epilogue also leaves "f1 > 0" as one bit per element - what the gated dX
-                # product of layer 2 reads instead of the 134 MB of f1)
-                if m.ffn_gate_mask and m.__dict__.get("_fwd_grad", False):
-                    fmask = K.gate_mask_buffer(Tn, m.dff, x.device)
-                    m.__dict__["_gate_mask_passes"] = m.__dict__.get("_gate_mask_passes", 0) + 1
-                f1 = K.gemm_hp(K.hp_view(hplanes, s_h2, Tn, D), sc["hp_1"],
-                               torch.empty(Tn, m.dff, dtype=torch.float32, device=x.device), bias=W(b + "pwff.layer1.bias"),
-                               flags=K.EPI_RELU, dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_HID, gate_mask_out=fmask)
-            else:
-                f1 = K.linear_fwd(h2, W(b + "pwff.layer1.weight"), W(b + "pwff.layer1.bias"), flags=K.EPI_RELU,
-                                  dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_HID,
-                                  **prod(i, 2, a_scale=s_h2, b_scale=sc and sc["rs_1"]))
-            use_b = sc is not None and not (off is not None and off[i, 1])          # f1 on its bound
-            # (few tokens: the K slices of this product go to the next layer's LayerNorm unreduced - kernels.PendingRows)
-            x3 = K.linear_fwd(f1, W(b + "pwff.layer2.weight"), W(b + "pwff.layer2.bias"), residual=x2, ldr=D,
-                              dropout_p=p, seed=seed, stream_id=sid + _SITE_FFN_OUT, defer_reduce=i + 1 < m.nlayers,
-                              **prod(i, 3, a_scale=sc["f1_scale"] if use_b else None, a_scale_stride=0 if use_b else 1,
-                                     b_scale=sc and sc["rs_2"]))
-            saved.append((x, mean1, rstd1, h1, qkv, att, lse, x2, mean2, rstd2, h2, f1, kbits, fmask, kv))
-            if measure_fwd:
-                gs = sc["guard_stats"][i]
-                K.weight_scales([dict(w=t, stats=gs[j], rows_only=True) for j, t in ((0, att), (1, f1), (3, h1), (4, h2))])
-            x = x3
+            x, acts = _layer_fwd(plan, m, flat, seq, i, x, hplanes)
+            saved.append(acts)
         pred = K.linear_fwd(x, W("output_projection.weight"), W("output_projection.bias"),
                             flags=K.EPI_TANH if m.use_tanh_out else 0, arith=ar)
-        if measure_fwd:
-            scales[0]["guard_stats"][:, 2].zero_()                 # dz1: not measured here (slack 0 = "as good as its bound")
-            K.fill_u32([(scales[0]["minbuf"], 0x7F000000)])        # ... and its scale slot reads "unused"
-            guard.submit(scales[0]["guard_stats"], scales[0]["ints"], scales[0]["minbuf"], scales, forward_only=True)
-        ctx.model, ctx.seed, ctx.seq, ctx.flat, ctx.arith, ctx.attn_arith = m, seed, seq, flat, ar, attn_default
-        ctx.p, ctx.pa = p, pa
-        ctx.guard, ctx.measure, ctx.off = guard, measure, ctx_off
-        ctx.use_hp = use_hp
-        ctx.saved, ctx.conv_saved, ctx.scales = saved, conv_saved, scales
-        # (NOT `ctx.pred = pred`: the output's grad_fn is this node, the node would hold the output - a reference cycle only the
-        # cyclic collector frees, at a time of its choosing, with everything else the node still holds.  A detached alias of the
-        # same storage carries no grad_fn.)
+        if plan.measure_fwd:
+            s0 = plan.scales[0]
+            s0["guard_stats"][:, 2].zero_()                 # dz1: not measured here (slack 0 = "as good as its bound")
+            K.fill_u32([(s0["minbuf"], 0x7F000000)])        # ... and its scale slot reads "unused"
+            plan.guard.submit(s0["guard_stats"], s0["ints"], s0["minbuf"], plan.scales, forward_only=True)
+        ctx.model, ctx.seq, ctx.flat, ctx.plan, ctx.saved, ctx.conv_saved = m, seq, flat, plan, saved, conv_saved
+        # (NOT `ctx.pred = pred`: the node would hold its own output - a reference cycle only the cyclic collector frees, at a
+        # time of its choosing, with everything else the node holds.  A detached alias of the same storage has no grad_fn.)
         ctx.x_last, ctx.pred = x, pred.detach()
         return pred
 
     @staticmethod
     def backward(ctx, dpred):
-        m, seed, seq, flat = ctx.model, ctx.seed, ctx.seq, ctx.flat
-        p, pa, ar = ctx.p, ctx.pa, ctx.arith
-        B, L = seq.shape
-        D, H = m.dlayer, m.nhead
+        if ctx.saved is None:
+            raise RuntimeError("EncoderOnlyTransformer: this graph's activations were freed by its first backward pass")
+        m, seq, flat, plan = ctx.model, ctx.seq, ctx.flat, ctx.plan
+        B, L, p, seed, ar = plan.B, plan.L, plan.p, plan.seed, plan.arith
         gflat = m._flat_grad
-        m.__dict__["_grad_dirty"] = True          # raw-pointer writes into the flat gradient buffer from here on (optim.py: zero_grad)
+        m.grads_written()
         W = lambda name: m._slice(flat, name)                                      # noqa: E731
         G = lambda name: m._slice(gflat, name)                                     # noqa: E731
-
-        ln_pending = []      # deferred (dgamma, dbeta) reductions of the LayerNorm backward kernels: one launch per flush
-        # Small batches: the weight-gradient products (independent of the dX chain, 40 % of the backward GEMM time) go to a
-        # side stream; the main stream waits for it before a gradient slice is handed on and at the end of the pass.
-        main = torch.cuda.current_stream(dpred.device)
-        side = None
-        if m.side_stream_dw and D >= 512 and B * L >= SIDE_STREAM_MIN_TOKENS and B * L * D <= SIDE_STREAM_MAX_WORK:
-            side = m.__dict__.get("_side_stream")
-            if side is None or side.device != dpred.device:
-                side = m.__dict__["_side_stream"] = torch.cuda.Stream(device=dpred.device)
-
-        # Operands the side stream reads were allocated on the main stream.  They are kept ALIVE here until the main stream has
-        # waited for the side stream (`join`, the end of the pass) instead of being handed to `record_stream`: blocks parked
-        # behind a side-stream event return to the allocator whenever the host happens to notice - the free lists of one step
-        # differed from the next one's and reserved memory crept (9.3 -> 9.9 GiB over 4,000 steps, profiles/r05/r05_soak.txt);
-        # with plain lifetimes every step allocates and frees in the same order.  (~3 GB more at the peak of 32 x 512.)
-        side_keep = []
-
-        def dw(*tensors_then_kwargs, **kw):
-            """K.linear_bwd_weight(dy, x, dw, db, ...) - on the side stream when there is one."""
-            if side is None:
-                return K.linear_bwd_weight(*tensors_then_kwargs, **kw)
-            side.wait_stream(main)                       # the operands were produced on the main stream
-            side_keep.extend(tensors_then_kwargs[:2])    # allocated on the main stream, read on the side stream
-            with torch.cuda.stream(side):
-                return K.linear_bwd_weight(*tensors_then_kwargs, **kw)
-
-        # The weight-gradient products of a layer go out in GROUPS when they run in f16x2 on uniform scales (ptamd_gemm_group:
-        # one launch whose work items fill the chip in whole rounds with a longer K per item and fewer slabs, one launch for all
-        # the split-K reductions) - their operands are only read afterwards.  m.dw_group: "pairs" = the two FFN products
-        # when both exist, the two attention products at the end of the layer (best where a pair fills a round on its own:
-        # 10.39 against 10.57 ms at 32 x 512, the whole layer as one group 10.63 - it starts late and runs three rounds);
-        # "layer" = all four at the end (best for few tokens, where the step is bound by launches: config 3 7.31 / 7.44 / 7.65
-        # ms as layer / pairs / one by one); "auto" picks by the size of the FFN pair; "off" = one by one.
-        queue = []
-        dw_group = m.dw_group if K.GROUP_DW else "off"
-        if dw_group == "auto":
-            ffn_tiles = -(-D // 256) * -(-m.dff // 128) + -(-m.dff // 256) * -(-D // 128)      # 256 x 128 tiles of dW2 and dW1
-            dw_group = "pairs" if ffn_tiles * B * L >= 256 * 2048 else "layer"
-
-        def dw_later(dy, x, gw, gb, arith=None, dy_scale=None, x_scale=None):
-            if dw_group == "off":
-                return dw(dy, x, gw, gb, arith=arith, dy_scale=dy_scale, x_scale=x_scale)
-            queue.append((dy, x, gw, gb, arith, dy_scale, x_scale))
-
-        def dw_flush():
-            jobs = list(queue)
-            queue.clear()
-            # members of a group: f16x2 on uniform scales (the top layer's FFN gradients come without - no fused LayerNorm
-            # backward above them - and go one by one, like everything in the other arithmetics)
-            ok = [j for j in jobs if j[5] is not None and j[6] is not None and j[1].shape[1] % 4 == 0]
-            tiles = sum(-(-j[0].shape[1] // 256) * -(-j[1].shape[1] // 128) for j in ok)
-            sk = K.pick_group_split(tiles, ok[0][0].shape[0]) if 2 <= len(ok) <= 4 else 0
-            if sk < 2:
-                ok = []
-            for dy, x, gw, gb, a, sy, sx in jobs:
-                if not any(dy is o[0] and x is o[1] for o in ok):
-                    dw(dy, x, gw, gb, arith=a, dy_scale=sy, x_scale=sx)
-            if not ok:
-                return
-            group = [(dy, x, gw, gb, sy, sx) for dy, x, gw, gb, a, sy, sx in ok]
-            if side is None:
-                return K.linear_bwd_weight_group(group, sk)
-            side.wait_stream(main)
-            for dy, x, *_ in ok:
-                side_keep.extend((dy, x))
-            with torch.cuda.stream(side):
-                K.linear_bwd_weight_group(group, sk)
-
-        def join():
-            if side is not None:
-                main.wait_stream(side)
-                side_keep.clear()                # (whatever is freed from here on is reused behind the side stream's work)
-
-        def done(first, last):
-            if m.grad_hook is not None:
-                K.layernorm_bwd_flush(ln_pending)     # a slice handed to the all-reduce must be final
-                o0, _ = m._layout[first]
-                o1, s1 = m._layout[last]
-                if side is None:
-                    m.grad_hook(o0, o1 + int(np.prod(s1)) - o0)
-                else:
-                    # the slice is final once BOTH streams are here: the collective is issued from the side stream behind a
-                    # wait for the main one, so the dX chain on the main stream does not stop for the weight-gradient products
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        m.grad_hook(o0, o1 + int(np.prod(s1)) - o0)
-
-        off, wide = ctx.off if ctx.off is not None else (None, None)
-
-        def prod(i, k, **scale_kw):      # as in forward: dX products 4..7 of AutoGuard.WIDE
-            if wide is not None and wide[i, k]:
-                return dict(arith=K.GEMM_BF16X3)
-            return dict(arith=ar, **scale_kw)
+        dws = _GradSchedule(m, plan, torch.cuda.current_stream(dpred.device))
         dpred = dpred.contiguous().view(-1, NUM_PREDICTED_ANGLES * 2)
         dpre = K.tanh_bwd(dpred, ctx.pred) if m.use_tanh_out else dpred
-        K.linear_bwd_weight(dpre, ctx.x_last, G("output_projection.weight"), G("output_projection.bias"),
-                            arith=ar)
+        K.linear_bwd_weight(dpre, ctx.x_last, G("output_projection.weight"), G("output_projection.bias"), arith=ar)
         dx = K.linear_bwd_input(dpre, W("output_projection.weight"), arith=ar)
-        done("output_projection.weight", "output_projection.bias")
-        scales = ctx.scales
-        fuse = D <= 1024                                   # LayerNorm backward + the dropout backward behind it in one kernel
-        i32 = lambda: torch.empty(B * L, dtype=torch.int32, device=dx.device)                 # noqa: E731
-        dy2 = s_dy2 = bs_dz1 = None                        # dropout'(dx) of the FFN output site, made by the layer above
-        attn_ar = ctx.attn_arith if m.attn_mode is None else int(m.attn_mode)
+        dws.done("output_projection.weight", "output_projection.bias")
+        scales = plan.scales
         s_dqkv_all = None
-        have_min = False                                   # ... together with the uniform scales of dy2 / dz1 for the dW products
         if scales is not None:
             # atomicMin targets of this backward pass (largest scale): the uniform scales of every layer and, where the f16x2
             # attention kernels leave the row scales of dqkv behind, those - one launch (ptamd_fill_u32) for both presets
             presets = [(scales[0]["minbuf"], 0x7F000000)]
-            if m.attn_row_scales and K.attention_row_scales_available(D // H, attn_ar):
+            if plan.attn_row_scales:
                 s_dqkv_all = torch.empty((m.nlayers, B * L), dtype=torch.int32, device=dpred.device)
                 presets.append((s_dqkv_all, 0x7F000000))
             K.fill_u32(presets)
-        # dX of FFN layer 2 on ptamd_gemm_hp: the fused LayerNorm backward that makes dy2 writes it a second time as planes
-        dy2_planes, have_planes = None, False
-        if ctx.use_hp and m.hp_dx and fuse and scales is not None and "hp_2t" in scales[0] and m.dff % 32 == 0:
-            dy2_planes = torch.empty(K.lib().ptamd_hp_bytes(B * L, D), dtype=torch.uint8, device=dx.device)
+        dy2_planes = torch.empty(K.lib().ptamd_hp_bytes(B * L, plan.D), dtype=torch.uint8, device=dx.device) if plan.hp_dx else None
+        carry = (dx, None, None, None, False, False)
         for i in reversed(range(m.nlayers)):
-            b = f"encoder.enc_layers.{i}."
-            sid = i * 8
-            sc = scales[i] if scales is not None else None
-            x, mean1, rstd1, h1, qkv, att, lse, x2, mean2, rstd2, h2, f1, kbits, fmask, kv = ctx.saved[i]
-            # x3 = x2 + drop(f1 W2^T + b2)
-            if dy2 is None:
-                dy2 = K.dropout_bwd(dx, p, seed, sid + _SITE_FFN_OUT) if p > 0 else dx
-                if sc is not None and fuse and m.top_layer_scales:
-                    # the top layer: no fused LayerNorm backward above it that would leave the uniform scales of dy2 / dz1
-                    # behind - one streaming pass over dy2 (largest |x| and largest row norm) and the same bound instead,
-                    # so that its two FFN weight-gradient products run in f16x2 like those of every other layer
-                    ts = sc["top_stats"]
-                    K.weight_scales([dict(w=dy2, stats=ts, rows_only=True)])
-                    K.bound_scales([dict(w=ts, w_index=2, out_scale=sc["dy2_min"]),
-                                    dict(ln_gamma=sc["dz1_factor_rec"], sqrt_d=1.0, w=ts, w_index=0, out_scale=sc["dz1_min"])])
-                    have_min = True
-            uni = sc is not None and have_min              # uniform scales of both operands: the dW product runs in f16x2
-            o_att, o_f1, o_dz1, o_h1, o_h2 = (bool(v) for v in off[i]) if off is not None else (False,) * 5   # AutoGuard
-            dw_later(dy2, f1, G(b + "pwff.layer2.weight"), G(b + "pwff.layer2.bias"), arith=ar,
-                                dy_scale=sc["dy2_min"] if uni and not o_f1 else None, x_scale=sc["f1_scale"] if uni and not o_f1 else None)
-            # backward of layer2 and, in its epilogue, of the ReLU + dropout in front of it (gate = saved f1)
-            if dy2_planes is not None and have_planes and not (wide is not None and wide[i, 7]):
-                # dy2 came from the fused LayerNorm backward of the layer above together with its planes: LDS-DMA kernel
-                dz1 = K.gemm_hp(K.hp_view(dy2_planes, s_dy2, B * L, D), sc["hp_2t"],
-                                torch.empty(B * L, m.dff, dtype=torch.float32, device=dx.device),
-                                residual=f1 if fmask is None else None, ldr=f1.stride(0) if fmask is None else 0,
-                                gate_mask=fmask, flags=K.EPI_GATE, gate_scale=1.0 / (1.0 - p))
-            else:
-                dz1 = K.linear_bwd_input(dy2, W(b + "pwff.layer2.weight"), gate=f1, gate_dropout_p=p, gate_mask=fmask,
-                                         **prod(i, 7, a_scale=s_dy2 if sc else None, b_scale=sc and sc["cs_2"]))
-            if ctx.measure:     # the true maxima of the five bound-scaled operands of this layer (AutoGuard; every 16th step)
-                gs = sc["guard_stats"][i]
-                K.weight_scales([dict(w=t, stats=gs[j], rows_only=True) for j, t in enumerate((att, f1, dz1, h1, h2))])
-            uni1 = uni and not (o_dz1 or o_h2)
-            dw_later(dz1, h2, G(b + "pwff.layer1.weight"), G(b + "pwff.layer1.bias"), arith=ar,
-                                dy_scale=sc["dz1_min"] if uni1 else None, x_scale=sc["h2_scale"] if uni1 else None)
-            if dw_group != "layer":
-                dw_flush()                                    # the two FFN products now, the two attention products at the end
-            # (few tokens: the K slices of dh2 / dh1 go to the fused LayerNorm backward unreduced - kernels.Slabs)
-            dh2 = K.linear_bwd_input(dz1, W(b + "pwff.layer1.weight"), defer_reduce=fuse,
-                                     **prod(i, 6, a_scale=bs_dz1 if sc and not o_dz1 else None, b_scale=sc and sc["cs_1"]))
-            # x2 = x + drop(att Wo^T + bo)
-            g2w, g2b = G(b + "sublayer_connections.1.norm.weight"), G(b + "sublayer_connections.1.norm.bias")
-            if fuse:
-                s_dyo = i32() if sc else None
-                dx2, dyo = K.layernorm_bwd_dropout(dh2, x2, W(b + "sublayer_connections.1.norm.weight"), mean2, rstd2, g2w, g2b,
-                                                   dx, p, seed, sid + _SITE_ATTN_OUT, row_scale=s_dyo,
-                                                   row_scale_min=sc["dyo_min"] if sc else None, pending=ln_pending)
-            else:
-                s_dyo = None
-                dx2 = K.layernorm_bwd(dh2, x2, W(b + "sublayer_connections.1.norm.weight"), mean2, rstd2, g2w, g2b, dres=dx,
-                                      pending=ln_pending)
-                dyo = K.dropout_bwd(dx2, p, seed, sid + _SITE_ATTN_OUT) if p > 0 else dx2
-            uni_o = sc is not None and fuse and not o_att
-            dw_later(dyo, att, G(b + "self_attn.wo.weight"), G(b + "self_attn.wo.bias"), arith=ar,
-                                dy_scale=sc["dyo_min"] if uni_o else None, x_scale=sc["att_scale"] if uni_o else None)
-            datt = K.linear_bwd_input(dyo, W(b + "self_attn.wo.weight"), **prod(i, 5, a_scale=s_dyo, b_scale=sc and sc["cs_o"]))
-            # the f16x2 attention kernels leave the row scales of dqkv (A of the dX product) and the smallest of them (the
-            # uniform scale of dqkv as operand of the dW product) behind; other arithmetics: one pass over dqkv
-            attn_scales = sc is not None and m.attn_row_scales and K.attention_row_scales_available(D // H, attn_ar)
-            s_dqkv = s_dqkv_all[i] if attn_scales else None
-            dqkv = K.attention_bwd(qkv, seq, att, datt, lse, H, pa, seed, sid + _SITE_ATTN, arith=attn_ar,
-                                    row_scale=s_dqkv, row_scale_min=sc["dqkv_min"] if attn_scales else None, keep_bits=kbits,
-                                    kv=kv)
-            gw, gb = m._qkv(gflat, i)
-            wqkv, _ = m._qkv(flat, i)
-            if sc is not None:
-                dq_uni = sc["dqkv_min"]
-                if not attn_scales:
-                    s_dqkv, dq_uni = i32(), sc["dqkv_scale"]
-                    K.weight_scales([dict(w=dqkv, row_scale=s_dqkv, stats=sc["dqkv_stats"], rows_only=True)])
-                    K.bound_scales([dict(w=sc["dqkv_stats"], w_index=2, out_scale=sc["dqkv_scale"])])
-                dw_later(dqkv, h1, gw, gb, arith=ar, dy_scale=None if o_h1 else dq_uni, x_scale=None if o_h1 else sc["h1_scale"])
-                dh1 = K.linear_bwd_input(dqkv, wqkv, defer_reduce=fuse and i > 0,
-                                         **prod(i, 4, a_scale=s_dqkv, b_scale=sc["cs_qkv"]))
-            else:
-                dw_later(dqkv, h1, gw, gb, arith=ar)
-                dh1 = K.linear_bwd_input(dqkv, wqkv, arith=ar, defer_reduce=fuse and i > 0)
-            g1w, g1b = G(b + "sublayer_connections.0.norm.weight"), G(b + "sublayer_connections.0.norm.bias")
-            if fuse and i > 0:      # the gradient enters layer i - 1 through ITS FFN-output dropout: made here, with its scales
-                s_dy2, bs_dz1 = (i32(), i32()) if scales is not None else (None, None)
-                below = scales[i - 1] if scales is not None else None
-                dx, dy2 = K.layernorm_bwd_dropout(dh1, x, W(b + "sublayer_connections.0.norm.weight"), mean1, rstd1, g1w, g1b,
-                                                  dx2, p, seed, (i - 1) * 8 + _SITE_FFN_OUT, row_scale=s_dy2,
-                                                  bound_factor=below["dz1_factor"] if below else None, bound_scale=bs_dz1,
-                                                  row_scale_min=below["dy2_min"] if below else None,
-                                                  bound_scale_min=below["dz1_min"] if below else None, pending=ln_pending,
-                                                  planes=dy2_planes if below else None)
-                have_min = below is not None
-                have_planes = below is not None and dy2_planes is not None
-            else:
-                dx = K.layernorm_bwd(dh1, x, W(b + "sublayer_connections.0.norm.weight"), mean1, rstd1, g1w, g1b, dres=dx2,
-                                     pending=ln_pending)
-                dy2 = s_dy2 = bs_dz1 = None
-                have_min = have_planes = False
-            dw_flush()
-            done(b + "self_attn.wq.weight", b + "sublayer_connections.1.norm.bias")
+            carry = _layer_bwd(plan, m, flat, gflat, seq, i, ctx.saved[i], carry, dws, s_dqkv_all, dy2_planes)
             ctx.saved[i] = None
-        K.layernorm_bwd_flush(ln_pending)
-        join()
-        if ctx.measure:
-            ctx.guard.submit(scales[0]["guard_stats"], scales[0]["ints"], scales[0]["minbuf"], scales)
+        dx = carry[0]
+        K.layernorm_bwd_flush(dws.ln_pending)
+        dws.join()
+        if plan.measure:
+            plan.guard.submit(scales[0]["guard_stats"], scales[0]["ints"], scales[0]["minbuf"], scales)
         # ---- front end
         if not m.use_embedding:
             dx = K.posenc_add_bwd(dx, p, seed)
@@ -1130,12 +1127,12 @@ class _EncoderFn(torch.autograd.Function):
                               G(f"encoder.conv_layers.{j}.bias"), need_dx=need_dx, arith=ar)
             ctx.conv_saved[j] = None
         if convs:
-            done("encoder.conv_layers.0.weight", f"encoder.conv_layers.{len(convs) - 1}.bias")
+            dws.done("encoder.conv_layers.0.weight", f"encoder.conv_layers.{len(convs) - 1}.bias")
         if m.use_embedding:
             K.embed_bwd(seq, dx, m.dmodel, p, seed, G("encoder.input_embedding.emb.weight"))
-            done("encoder.input_embedding.emb.weight", "encoder.input_embedding.emb.weight")
-        ctx.saved = ctx.conv_saved = ctx.x_last = ctx.pred = ctx.scales = None      # (whatever still refers to this node holds no activations)
-        return None, None, None, None
+            dws.done("encoder.input_embedding.emb.weight", "encoder.input_embedding.emb.weight")
+        ctx.saved = ctx.conv_saved = ctx.x_last = ctx.pred = ctx.plan = None    # (whatever still refers to this node holds no activations)
+        return None, None, None, None, None
 
 
 # tokens x d_model below which AUTO runs the whole step in bf16x3: the scale bookkeeping of f16x2 costs more than its products
@@ -1149,9 +1146,9 @@ AUTO_F16X2_MIN_WORK = 1 << 20
 # (profiles/r03/r03_ab_side_stream.txt), but +14 % on config 2 (4096 x 256) and +12 % on config 1, where the step is bound by
 # host-side launches and the stream joins add to them
 SIDE_STREAM_MAX_WORK = 1 << 23
-SIDE_STREAM_MIN_TOKENS = int(os.environ.get("PTAMD_SIDE_MIN_TOKENS", 4096))     # (the environment variable: for measurements)
+SIDE_STREAM_MIN_TOKENS = 4096
 # tokens from which the products behind a LayerNorm run on ptamd_gemm_hp (below: ptamd_gemm, 128-row tiles)
-HP_MIN_TOKENS = int(os.environ.get("PTAMD_HP_MIN_TOKENS", 4096))     # (the environment variable: for measurements)
+HP_MIN_TOKENS = 4096
 
 
 class EncoderOnlyTransformer(_TransformerBase):

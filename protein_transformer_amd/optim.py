@@ -27,19 +27,15 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=False):
         _, g = self.model.flat_parameters()
-        # nothing to do when the last step zeroed this very buffer and nothing has written it since: no backward pass of the
-        # model (raw-pointer writes: `_grad_dirty`), no torch op on it or on a `p.grad` view (their shared version counter)
-        if (self._zeroed == (g.data_ptr(), g._version) and not self.model.__dict__.get("_grad_dirty", True)):
+        # nothing to do when the last step zeroed this very buffer and nothing has written it since: no raw-pointer writer
+        # (the backward pass, a collective: `model.grads_written`), no torch op on it or on a `p.grad` view
+        if self._zeroed == self.model.grads_stamp():
             return
         g.zero_()
         self._zeroed = None
 
-    def _after_step(self, g, zeroed):
-        if zeroed:
-            self.model.__dict__["_grad_dirty"] = False
-            self._zeroed = (g.data_ptr(), g._version)
-        else:
-            self._zeroed = None
+    def _after_step(self, zeroed):
+        self._zeroed = self.model.grads_stamp() if zeroed else None
 
     def clip_grad_norm_(self, max_norm):
         """Device-side `clip_grad_norm_`: launches the squared-norm reduction and arms the next `step()`
@@ -92,7 +88,7 @@ class FusedSGD(_FlatOptimizer):
             plan.sgd_step(w, g, sq, mx, grp["lr"], grp["weight_decay"], with_planes=with_planes, zero_grad=zero)
             self._written()
             mark_fresh()        # (after the bump: only the cache this step prepared carries the new stamp)
-        self._after_step(g, zero)
+        self._after_step(zero)
 
 
 class FusedAdam(_FlatOptimizer):
@@ -129,7 +125,7 @@ class FusedAdam(_FlatOptimizer):
             self._written()
             plan.prepare(w, with_planes=with_planes)
             mark_fresh()
-        self._after_step(g, zero)
+        self._after_step(zero)
 
     def state_dict(self):
         sd = super().state_dict()

@@ -445,6 +445,37 @@ def test_weight_gradient_grouping_modes(dev):
         assert d < 2e-6, (mode, d)
 
 
+def test_backward_follows_its_forward_pass(dev):
+    """Backward runs what its forward pass decided: the model's path-selecting attributes changed between the forward pass
+    and `backward()` change nothing, bit for bit (the K / V planes, keep bits, gate masks and planes of the forward pass were
+    made for the settings it saw)."""
+    from protein_transformer_amd import kernels as K
+    grads = []
+    for change in (False, True):
+        model, batch = _setup(dev, 2, 8, 512, 2048, [512] * 8, seed=43, dropout=0.1)
+        seq = batch[0].to(dev)
+        for step in range(2):
+            model.zero_grad()
+            loss = model(seq).square().mean()
+            if change and step == 1:
+                model.attn_mode, model.hp_dx, model.attn_row_scales = K.GEMM_BF16X3, False, False
+                model.side_stream_dw, model.dw_group = False, "off"
+            loss.backward()
+            model.auto_guard.settle()        # (the second pass on the trusted path: f16x2 scales, planes, groups)
+        assert model.__dict__.get("_side_stream") is not None
+        grads.append(model.flat_parameters()[1].clone())
+    assert torch.equal(grads[0], grads[1])
+
+
+def test_second_backward_raises(dev):
+    """A second backward pass through one graph: a clear error instead of a TypeError on the released activations."""
+    model, batch = _setup(dev, 1, 8, 64, 128, [32] * 2, seed=3)
+    loss = model(batch[0].to(dev)).sum()
+    loss.backward()
+    with pytest.raises(RuntimeError, match="freed by its first backward pass"):
+        loss.backward()
+
+
 _FIVE_STEPS = r"""
 import hashlib, json, sys, types
 import torch

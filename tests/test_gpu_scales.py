@@ -325,10 +325,9 @@ def test_weights_prep_matches_separate_launches(dev):
     from protein_transformer_amd import kernels as K
     m, _ = _prep_model(dev)
     flat, _ = m.flat_parameters()
-    m.__dict__["_fwd_grad"] = True
     m.weights_prep = False
-    ref = _snapshot(m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True))
-    for L in m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=False):      # scribble over everything the prep pass has to write
+    ref = _snapshot(m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True))
+    for L in m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=False, backward=True):      # scribble over everything the prep pass has to write
         for k in ("rs_qkv", "cs_qkv", "rs_o", "cs_o", "rs_1", "cs_1", "rs_2", "cs_2", "att_scale", "f1_scale", "h1_scale", "h2_scale"):
             L[k].fill_(-7)
         L["dz1_factor"].fill_(-1.0)
@@ -337,17 +336,17 @@ def test_weights_prep_matches_separate_launches(dev):
     m.weights_prep = True
     for rep in range(3):
         m._forget_prepared_weights()
-        got = _snapshot(m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True))
+        got = _snapshot(m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True))
         torch.cuda.synchronize()
         for key, want in ref.items():
             assert torch.equal(got[key], want), (rep, key, int((got[key] != want).sum()))
     assert m.__dict__["_prep_launches"] == 3
     # nothing has touched the weights: the next pass launches nothing; an in-place torch op on a parameter is noticed
-    m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True)
+    m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True)
     assert m.__dict__["_prep_launches"] == 3
     with torch.no_grad():
         dict(m.named_parameters())["encoder.enc_layers.1.pwff.layer2.weight"][5, 7] = 1000.0
-    L = m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True)
+    L = m._step_scales(flat, K.GEMM_AUTO, 0.1, 0.1, hp=True, backward=True)
     assert m.__dict__["_prep_launches"] == 4
     assert as_float(L[1]["cs_2"])[7] == scale_of(np.float32(1000.0)) and as_float(L[1]["rs_2"])[5] == scale_of(np.float32(1000.0))
 
@@ -383,8 +382,7 @@ def test_optimizer_step_prepares_the_next_pass(dev, optimizer):
     flat, _ = m.flat_parameters()
     left = _snapshot(m.__dict__["_train_cache"][0]["layers"])
     m._forget_prepared_weights()
-    m.__dict__["_fwd_grad"] = True
-    again = _snapshot(m._step_scales(flat, K.GEMM_AUTO, m.dropout, m.attn_dropout, hp=True))
+    again = _snapshot(m._step_scales(flat, K.GEMM_AUTO, m.dropout, m.attn_dropout, hp=True, backward=True))
     for key, want in again.items():
         assert torch.equal(left[key], want), key
 
