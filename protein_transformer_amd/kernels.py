@@ -94,7 +94,9 @@ def get_gemm_mode():
 
 class HpOperand:
     """An fp32 matrix [rows, K] in the pre-split "half-pair" format of include/ptamd.h (two f16 planes in MFMA-operand
-    blocks + one power-of-two scale per row): what ptamd_gemm_hp reads by LDS-DMA."""
+    blocks + one power-of-two scale per row): what ptamd_gemm_hp reads by LDS-DMA.  `scale` has ptamd_hp_padded_rows(rows)
+    entries: the writers of the format (ptamd_hp_split, ptamd_hp_split_rows) set the padding rows' scales too, and a view
+    over a longer buffer (hp_view) has to cover them (hp_split_rows checks)."""
     __slots__ = ("planes", "scale", "rows", "K")
 
     def __init__(self, rows, K, device):
@@ -396,6 +398,8 @@ def hp_split_rows(mats, outs):
         arr = (HpSplitJob * len(chunk))()
         for k, (w, o) in enumerate(chunk):
             assert w.dim() == 2 and w.stride(1) == 1 and (o.rows, o.K) == tuple(w.shape)
+            # (the kernel writes ptamd_hp_padded_rows(rows) scales: the view must own the padding rows' entries too)
+            assert o.scale.numel() >= lib().ptamd_hp_padded_rows(o.rows), "hp_split_rows: no room for the padding rows' scales"
             arr[k] = HpSplitJob(x=w.data_ptr(), ld=w.stride(0), rows=w.shape[0], K=w.shape[1], planes=o.planes.data_ptr(),
                                 scale=o.scale.data_ptr())
         check(lib().ptamd_hp_split_rows(arr, len(chunk), stream()), "hp_split_rows")

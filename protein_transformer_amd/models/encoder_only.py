@@ -547,7 +547,10 @@ class _TransformerBase(nn.Module):
         cache = caches.get(key)
         if cache is None:
             dev = flat.device
-            n_i = self.nlayers * (8 * D + 2 * F + 5 * 4)              # int32: weight scales + 5 uniform scales (4 copies each) per layer
+            # W1's row scales are also the scale array of its hp planes (below), which has ptamd_hp_padded_rows(F) entries: the
+            # split writes the padding rows' scales too, so they get room of their own (`rs_1p`) instead of landing on cs_1
+            Fp = -(-F // 32) * 32
+            n_i = self.nlayers * (8 * D + F + Fp + 5 * 4)             # int32: weight scales + 5 uniform scales (4 copies each) per layer
             ints = torch.zeros(n_i, dtype=torch.int32, device=dev)
             stats = torch.zeros(self.nlayers, 9, 4, dtype=torch.float32, device=dev)
             factor = torch.zeros(self.nlayers, 4, dtype=torch.float32, device=dev)    # [i, 2] = dz1_factor (a stats-shaped record)
@@ -565,9 +568,10 @@ class _TransformerBase(nn.Module):
             for i in range(self.nlayers):
                 b = f"encoder.enc_layers.{i}."
                 wqkv, bqkv = self._qkv(flat, i)
-                L = dict(rs_qkv=take(3 * D), cs_qkv=take(D), rs_o=take(D), cs_o=take(D), rs_1=take(F), cs_1=take(D),
+                L = dict(rs_qkv=take(3 * D), cs_qkv=take(D), rs_o=take(D), cs_o=take(D), rs_1p=take(Fp), cs_1=take(D),
                          rs_2=take(D), cs_2=take(F), att_scale=take(4), f1_scale=take(4), h1_scale=take(4), h2_scale=take(4),
                          dqkv_scale=take(4), dz1_factor=factor[i, 2:3], dz1_factor_rec=factor[i])
+                L["rs_1"] = L["rs_1p"][:F]
                 L.update(dy2_min=minbuf[i, 0:4], dz1_min=minbuf[i, 4:8], dyo_min=minbuf[i, 8:12], dqkv_min=minbuf[i, 12:16])
                 st = stats[i]
                 wjobs += [dict(w=wqkv, row_scale=L["rs_qkv"], col_scale=L["cs_qkv"]),
@@ -611,7 +615,7 @@ class _TransformerBase(nn.Module):
                 for i, L in enumerate(layers):
                     w1 = W(f"encoder.enc_layers.{i}.pwff.layer1.weight")
                     # (the planes' row scales ARE the rows' f16x2 scales: one array serves the staging GEMM and ptamd_gemm_hp)
-                    L["hp_1"] = K.hp_view(torch.empty(K.lib().ptamd_hp_bytes(F, D), dtype=torch.uint8, device=dev), L["rs_1"], F, D)
+                    L["hp_1"] = K.hp_view(torch.empty(K.lib().ptamd_hp_bytes(F, D), dtype=torch.uint8, device=dev), L["rs_1p"], F, D)
                     L["hp_qkv"] = K.hp_view(torch.empty(K.lib().ptamd_hp_bytes(3 * D, D), dtype=torch.uint8, device=dev),
                                             L["rs_qkv"], 3 * D, D)
                     cache["hp_mats"] += [w1, self._qkv(flat, i)[0]]
