@@ -443,7 +443,8 @@ int ptamd_embed_bwd(const int64_t *seq, const float *dout, int B, int L, int D, 
                     float *demb, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Fused masked multi-head attention (Attention.py:14-22,55-69), scores never materialised.  `arith` (head sizes 64
- * and 32; other head sizes always run the exact-f32 kernels):
+ * and 32; head size 128 has f16x2 and exact-f32 kernels, its bf16x3 requests run the exact-f32 ones; head sizes 8 and 16
+ * always run the exact-f32 kernels):
  *   PTAMD_GEMM_F32                 the exact-f32 MFMA kernels;
  *   PTAMD_GEMM_BF16X3 / _FULL      operands split exactly into three bf16 terms, six products on the bf16 matrix pipe;
  *   PTAMD_GEMM_F16X2 / _AUTO       operands scaled by powers of two and split into two f16 terms, three products on the
@@ -452,12 +453,12 @@ int ptamd_embed_bwd(const int64_t *seq, const float *dout, int B, int L, int D, 
  *                                  element); the scales are found inside the kernels, nothing is added to the interface.
  *   qkv [T,3D]: Q | K | V column blocks, head h at columns h*dk..; key-padding mask from seq != 20;
  *   softmax(QK^T/sqrt(dk)) with dropout p on the probabilities; out [T,D] heads merged.
- *   lse [B,H,L] saves log-sum-exp per query row for the backward. dk must be 32 or 64.
+ *   lse [B,H,L] saves log-sum-exp per query row for the backward. dk must be 8, 16, 32, 64 or 128.
  *   ptamd_attention_bwd, row_scale [T] / row_scale_min [4] (optional, both or only the first; f16x2 arithmetic with
- *   dk 32 / 64 only, PTAMD_ERR_BAD_SHAPE otherwise): the f16x2 row scales of dqkv (ptamd_gemm a_scale) and the smallest
+ *   dk 32 / 64 / 128 only, PTAMD_ERR_BAD_SHAPE otherwise): the f16x2 row scales of dqkv (ptamd_gemm a_scale) and the smallest
  *   of them (4 copies: a uniform scale, stride 0), accumulated with atomicMin - preset both to 0x7F000000.
- *   keep_bits (optional, f16x2 arithmetic with dk 32 / 64 only, PTAMD_ERR_BAD_SHAPE otherwise; ptamd_attention_keep_bits_bytes
- *   bytes): the dropout decisions of the probabilities, written by ptamd_attention_fwd and handed to ptamd_attention_bwd by
+ *   keep_bits (optional, f16x2 arithmetic with dk 32 / 64 / 128 only, PTAMD_ERR_BAD_SHAPE otherwise;
+ *   ptamd_attention_keep_bits_bytes bytes): the dropout decisions of the probabilities, written by ptamd_attention_fwd and handed to ptamd_attention_bwd by
  *   the caller (the library keeps nothing between calls), so that the backward kernel reads one word per key and 32
  *   queries instead of drawing the counter hash again: word [(b, h)][q / 32][key] (keys padded to a multiple of 32),
  *   bit q % 32 = 1 where query q keeps key.  The decisions are the generator's (csrc/attn_dropout.h) either way: a

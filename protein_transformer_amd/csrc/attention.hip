@@ -5,7 +5,8 @@
 // (scores = QK^T / sqrt(dk); masked_fill(key is padding, -inf); softmax; dropout(p) on the probabilities; P V)
 // without ever materialising the [B,H,L,L] score tensor (268 MB at B=32, L=512) and its autograd copies.
 //
-// Design (wave64, v_mfma_f32_32x32x2_f32, exact f32):
+// Design (wave64, v_mfma_f32_32x32x2_f32, exact f32; head sizes 8, 16, 32, 64 and 128 - the reference arithmetic of
+// head size 128, which also serves its bf16x3 requests):
 //   * forward / dQ kernels: one workgroup = (protein, head, 128 queries), 4 wavefronts x 32 queries.  K/V tiles
 //     of 64 keys are staged once per workgroup in LDS (register double buffering, one barrier per tile).
 //     Scores are computed TRANSPOSED, S^T[key][q] = mfma(K, Q): the MFMA C layout then puts one query per
@@ -45,6 +46,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int QB = 128;  // queries (or keys) per workgroup
 constexpr int KT = 64;   // keys per LDS tile in the forward / dQ kernels
 constexpr int QT = 32;   // queries per LDS tile in the dK/dV kernel
+
+// waves per SIMD the kernels are compiled for: head size 128 has 132 KB of LDS (one workgroup per CU: one wavefront per
+// SIMD) and row fragments of 64 floats, so it takes the whole register file
+template <int DK>
+constexpr int F32_WAVES = DK == 128 ? 1 : 2;
 
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 // row index inside a 32x32 MFMA C tile held by (register r, lane half lh)
@@ -92,7 +98,7 @@ __device__ __forceinline__ void load_row_frag(const float *__restrict__ base, in
 
 // =================================================================================================== forward
 template <int DK>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+__global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_fwd_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
                                                        int L, int H, float p_drop, uint64_t seed, uint32_t stream_id,
                                                        float *__restrict__ out, float *__restrict__ lse) {
   constexpr int LDK = DK + 1, NS = DK / 2, NDT = (DK + 31) / 32;
@@ -224,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const float *__restric
 // =================================================================================================== backward
 // dQ: same decomposition as the forward kernel
 template <int DK>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+__global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dq_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
                                                           const float *__restrict__ o_fwd, const float *__restrict__ d_o,
                                                           const float *__restrict__ lse, float *__restrict__ delta, int L,
                                                           int H, float p_drop, uint64_t seed, uint32_t stream_id,
@@ -348,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const float *__rest
 
 // dK, dV: one workgroup = 128 keys of one (protein, head); lane column = key
 template <int DK>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+__global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dkv_kernel(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
                                                            const float *__restrict__ d_o, const float *__restrict__ lse,
                                                            const float *__restrict__ delta, int L, int H, float p_drop,
                                                            uint64_t seed, uint32_t stream_id, float *__restrict__ dqkv) {
@@ -524,7 +530,7 @@ int ptamd_attention_fwd(const float *qkv, const int64_t *seq, int B, int L, int 
   if (dropout_p < 0.f || dropout_p >= 1.f) return PTAMD_ERR_BAD_SHAPE;
   if (!pt_aligned16(qkv) || !pt_aligned16(out)) return PTAMD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const bool f16x2 = (dk == 64 || dk == 32) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2);
+  const bool f16x2 = (dk == 64 || dk == 32 || dk == 128) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2);
   if (keep_bits && !f16x2) return PTAMD_ERR_BAD_SHAPE;  // the decisions are a by-product of the f16x2 kernels only
   if (kv_planes && !(f16x2 && kv_inv && pt_aligned16(kv_planes))) return PTAMD_ERR_BAD_SHAPE;   // ... the planes their input only
   if (f16x2) return pt_attention_fwd_f16x2(qkv, seq, B, L, H, dk, dropout_p, seed, stream_id, out, lse, keep_bits, kv_planes, kv_inv, st);
@@ -535,6 +541,7 @@ int ptamd_attention_fwd(const float *qkv, const int64_t *seq, int B, int L, int 
     case 16: return launch_fwd<16>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
     case 32: return launch_fwd<32>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
     case 64: return launch_fwd<64>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
+    case 128: return launch_fwd<128>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
     default: return PTAMD_ERR_BAD_SHAPE;
   }
 }
@@ -549,7 +556,7 @@ int ptamd_attention_bwd(const float *qkv, const int64_t *seq, const float *out, 
   if (!pt_aligned16(qkv) || !pt_aligned16(out) || !pt_aligned16(dout) || !pt_aligned16(dqkv)) return PTAMD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   float *delta = static_cast<float *>(workspace);
-  if ((dk == 64 || dk == 32) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2))
+  if ((dk == 64 || dk == 32 || dk == 128) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2))
     return pt_attention_bwd_f16x2(qkv, seq, out, dout, lse, delta, B, L, H, dk, dropout_p, seed, stream_id, dqkv, row_scale,
                                   row_scale ? row_scale_min : nullptr, keep_bits, kv_planes, kv_inv, delta + delta_floats(B, L, H),
                                   workspace_bytes / sizeof(float) - delta_floats(B, L, H), st);
@@ -561,6 +568,7 @@ int ptamd_attention_bwd(const float *qkv, const int64_t *seq, const float *out, 
     case 16: return launch_bwd<16>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
     case 32: return launch_bwd<32>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
     case 64: return launch_bwd<64>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
+    case 128: return launch_bwd<128>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
     default: return PTAMD_ERR_BAD_SHAPE;
   }
 }

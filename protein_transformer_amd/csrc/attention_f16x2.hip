@@ -23,6 +23,13 @@
 // Decomposition, LDS format, dropout hash and prefetching are those of attention_split.hip (8 wavefronts = 256 queries
 // or keys per workgroup, 32-row tiles, scores transposed so that a soft-max row is lane-local), with two planes per
 // tile instead of three (48 KB of LDS instead of 72).
+// Head size 128: a tile is two 64-column images of the dk = 64 layout ("column halves", HALVES below) that SHARE the
+// scale of a group of four rows: a staging thread holds the same float4 of both halves, so four rows are still one
+// wavefront and the group maximum is taken over all 128 columns.  The products whose rows come from the tile (S^T, dP^T)
+// then contract over both halves into one accumulator with the same four per-lane constants, and each product that
+// contracts over the tile rows is two independent 64-column output blocks with the dk = 64 register operand.  96 KB of
+// LDS per {K, V} (or {Q, dO}) double buffer: one workgroup per CU, so the backward kernels run one wavefront per SIMD
+// with the whole register file (their operands alone are 256 registers per lane).
 #include <stdlib.h>
 
 #include "attn_dropout.h"
@@ -211,9 +218,12 @@ __device__ __forceinline__ float load_row_planes(const char *__restrict__ planes
 // A group of four rows is held by 4 DK / 4 adjacent lanes (one wavefront for DK = 64, half of one for DK = 32); its
 // inverse scale goes to inv[(g & 1) * 4 + (g >> 1)], g = row >> 2, so that a lane half reads ITS four groups
 // (g = 2 j + lh) as one float4.  Loads are unconditional (row clamped); rows beyond nrows are zeroed when stored.
+// DK = 128 (two column halves): a thread's float4 of the first half has the same row and column as that of the second.
+template <int DK>
+constexpr int HALVES = DK > 64 ? DK / 64 : 1;      // 64-column tile images of a DK-wide tile
 template <int DK, int NW>
 struct StageGeo {
-  static constexpr int CPR = DK / 4;               // float4 per tile row
+  static constexpr int CPR = DK / HALVES<DK> / 4;  // float4 per tile row (of one column half)
   static constexpr int RPP = 64 * NW / CPR;        // tile rows the workgroup covers with one float4 per thread
   static constexpr int NI = RPP >= TR ? 1 : TR / RPP;  // float4 per thread and tile
 };
@@ -249,6 +259,53 @@ struct Stage {
     }
   }
 };
+// DK = 128: a thread stages the float4 at the same place of both column halves; the LDS image is [half][TILE image], and
+// the group scale covers both halves (one wavefront: four rows x 16 lanes, two float4 per lane)
+template <int NW, typename TILE>
+struct Stage<128, NW, TILE> {
+  using G = StageGeo<128, NW>;
+  static constexpr int CPR = G::CPR, NI = G::NI;
+  float4 v[NI][2];
+  __device__ __forceinline__ void load(const float *__restrict__ base, const TileOff<NI> &off) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) v[i][hf] = *reinterpret_cast<const float4 *>(base + off.o[i] + 64 * hf);
+  }
+  __device__ __forceinline__ void store(unsigned short *__restrict__ s, float *__restrict__ inv, int row0, int nrows,
+                                        int tid) const {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int row = tid / CPR + i * G::RPP;
+      const bool ok = row < TR && row0 + row < nrows;
+      float4 x[2];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        x[hf] = make_float4(ok ? v[i][hf].x : 0.f, ok ? v[i][hf].y : 0.f, ok ? v[i][hf].z : 0.f, ok ? v[i][hf].w : 0.f);
+      const uint32_t amax = group_umax<4 * CPR>(max(umax4(x[0]), umax4(x[1])));
+      const uint32_t sbits = pt_row_scale_bits(amax);
+      if (row < TR) {  // (wavefront-uniform)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) TILE::store4(s + hf * TILE::ELEMS, row, (tid % CPR) * 4, x[hf], __uint_as_float(sbits));
+        if ((tid % (4 * CPR)) == 0) {
+          const int g = row >> 2;
+          inv[(g & 1) * 4 + (g >> 1)] = __uint_as_float((254u << 23) - sbits);
+        }
+      }
+    }
+  }
+};
+// DK = 128: row fragments (d = 16 st + 8 lh + 0..7) and transposed fragments (columns 32 t + 0..31) of a staged tile - the
+// column half and the place inside it.  (The dk = 64 / 32 kernels call TILE::frag_rows / frag_cols directly: through this
+// extra inline level their instructions would come out in a different order.)
+template <typename TILE>
+__device__ __forceinline__ void tile_frag_rows(const unsigned short *__restrict__ s, int st, int lane, f16x8 (&f)[2]) {
+  TILE::frag_rows(s + (st >> 2) * TILE::ELEMS, st & 3, lane, f);
+}
+template <typename TILE>
+__device__ __forceinline__ void tile_frag_cols(const unsigned short *__restrict__ s, int kb, int t, int lane, f16x8 (&f)[2]) {
+  TILE::frag_cols(s + (t >> 1) * TILE::ELEMS, kb, 32 * (t & 1), lane, f);
+}
 
 // Element offsets of a thread's float4 in consecutive 32-row tiles of a [nrows, ld] block (rows clamped to the last one):
 // an add and a min per load instead of a 64-bit multiply; tiles that share rows (K and V, same ld) share them.
@@ -332,6 +389,10 @@ __device__ __forceinline__ void publish_row_scale(float amax, bool ok, int row, 
 
 constexpr float BSCALE0 = 1.329227995784916e36f;  // 2^120
 
+// 1 / sqrt(dk) of the scores
+template <int DK>
+constexpr float attn_scale() { return DK == 128 ? 0.08838834764831845f : DK == 64 ? 0.125f : 0.17677669529663687f; }
+
 constexpr int BUF = 2 * Tile2::ELEMS;  // f16 elements of one {A, B} tile buffer
 constexpr size_t ATTN_LDS = (size_t)2 * BUF * sizeof(unsigned short);
 
@@ -339,9 +400,12 @@ constexpr size_t ATTN_LDS = (size_t)2 * BUF * sizeof(unsigned short);
 #ifndef PT_ATTN_FWD_WAVES
 #define PT_ATTN_FWD_WAVES 2   // wavefronts per SIMD the forward kernel is compiled for (4 = 128 VGPRs: 27 spilled, measured in round 4)
 #endif
+// Head size 128 at 4 wavefronts (one per SIMD: 96 KB of LDS allow one workgroup per CU) is compiled for the whole register file.
+template <int DK, int NW>
+constexpr int FWD_WAVES = DK == 128 && NW == 4 ? 1 : PT_ATTN_FWD_WAVES;
 // TILE: the LDS image of a staged tile - Tile2 (padded rows) or Tile2U (unpadded, swizzled: what lets PARTS = 4 fit)
 template <int DK, int NW, int PARTS, typename TILE = Tile2>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD_WAVES, PT_ATTN_FWD_WAVES))) void attn_fwd_f16x2_kernel(
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAVES<DK, NW>, FWD_WAVES<DK, NW>))) void attn_fwd_f16x2_kernel(
     const float *__restrict__ qkv, const int64_t *__restrict__ seq, int L, int H, float p_drop, uint64_t seed,
     uint32_t stream_id, float *__restrict__ out, float *__restrict__ lse, uint32_t *__restrict__ keep_bits) {
   extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
@@ -357,7 +421,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
   const int q = q0 + l31;
   const bool q_ok = q < L;
   constexpr int KS = DK / 16, NT = DK / 32;
-  const float scale = DK == 64 ? 0.125f : 0.17677669529663687f;  // 1 / sqrt(dk)
+  const float scale = attn_scale<DK>();  // 1 / sqrt(dk)
   const AttnDrop dk_ = make_attn_drop(seed, stream_id, (uint32_t)(b * H + h), p_drop);
   const uint32_t q_part = attn_q_part(dk_, (uint32_t)q);
 
@@ -373,7 +437,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
   float m_run = -INFINITY, l_run = 0.f;  // running maximum in log2 units
   float v_run = 0.f;                     // largest inverse V group scale so far (a power of two; wavefront-uniform)
 
-  constexpr int TBUF = 2 * TILE::ELEMS;  // f16 elements of one {K, V} tile buffer
+  constexpr int TE = HALVES<DK> * TILE::ELEMS;  // f16 elements of one staged tile
+  constexpr int TBUF = 2 * TE;                   // ... of one {K, V} tile buffer
   Stage<DK, NW, TILE> stK[PARTS], stV[PARTS];
   const int ntiles = ((L + TR - 1) / TR + PARTS - 1) / PARTS;  // tiles of one part: part p walks tiles p ntiles ..
   auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * TBUF; };
@@ -394,7 +459,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
     stK[pt].load(base + D, toff);
     stV[pt].load(base + 2 * D, toff);
     stK[pt].store(tile(0, pt), sInvK[0][pt], pt * ntiles * TR, L, tid);
-    stV[pt].store(tile(0, pt) + TILE::ELEMS, sInvV[0][pt], pt * ntiles * TR, L, tid);
+    stV[pt].store(tile(0, pt) + TE, sInvV[0][pt], pt * ntiles * TR, L, tid);
     publish_mask(pt * ntiles * TR, 0, pt);
     const auto toff2 = rows[pt].next();
     stK[pt].load(base + D, toff2);
@@ -405,7 +470,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
   for (int kt = 0; kt < ntiles; ++kt) {
     const int k0 = (part * ntiles + kt) * TR, cur = kt & 1;
     const bool more = kt + 1 < ntiles;
-    const unsigned short *sK = tile(cur, part), *sV = sK + TILE::ELEMS;
+    const unsigned short *sK = tile(cur, part), *sV = sK + TE;
 #pragma unroll
     for (int pt = 0; pt < PARTS; ++pt) {
       const auto toff = rows[pt].next();
@@ -420,7 +485,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
 #pragma unroll
     for (int st = 0; st < KS; ++st) {  // S^T[key][q] = K Q^T (scaled operands)
       f16x8 kf[2];
-      TILE::frag_rows(sK, st, lane, kf);
+      if constexpr (HALVES<DK> == 1) TILE::frag_rows(sK, st, lane, kf);  // (dk = 64 / 32 written out: same instructions)
+      else tile_frag_rows<TILE>(sK, st, lane, kf);
       s = mfma3(kf, qf[st], s);
     }
     if (more) {  // scale + split + store the next tile(s) into the other buffer while the soft-max runs
@@ -428,7 +494,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
       for (int pt = 0; pt < PARTS; ++pt) {
         const int kn = (pt * ntiles + kt + 1) * TR;
         stK[pt].store(tile(cur ^ 1, pt), sInvK[cur ^ 1][pt], kn, L, tid);
-        stV[pt].store(tile(cur ^ 1, pt) + TILE::ELEMS, sInvV[cur ^ 1][pt], kn, L, tid);
+        stV[pt].store(tile(cur ^ 1, pt) + TE, sInvV[cur ^ 1][pt], kn, L, tid);
         publish_mask(kn, cur ^ 1, pt);
       }
     }
@@ -495,7 +561,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(PT_ATTN
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         f16x8 vf[2];
-        TILE::frag_cols(sV, 16 * m, 32 * t, lane, vf);
+        if constexpr (HALVES<DK> == 1) TILE::frag_cols(sV, 16 * m, 32 * t, lane, vf);
+        else tile_frag_cols<TILE>(sV, 16 * m, t, lane, vf);
         o[t] = mfma3(vf, pf, o[t]);
       }
     }
@@ -770,10 +837,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
 }
 
 // =================================================================================================== backward
+// (head size 128: 4 wavefronts, one workgroup per CU - see the header; the Q and dO (K and V) operands are 128 registers)
+template <int DK>
+constexpr int BWD_WAVES = DK == 128 ? 1 : 2;
 // dQ: same decomposition as the forward kernel.  Also computes delta[q] = sum_d dO[q,d] O[q,d] and publishes it for the
 // dK/dV kernel, which runs after this one on the same stream.
 template <int DK, int NW, int PARTS>
-__global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dq_f16x2_kernel(
+__global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_WAVES<DK>, BWD_WAVES<DK>))) void attn_bwd_dq_f16x2_kernel(
     const float *__restrict__ qkv, const int64_t *__restrict__ seq, const float *__restrict__ o_fwd,
     const float *__restrict__ d_o, const float *__restrict__ lse, float *__restrict__ delta, int L, int H, float p_drop,
     uint64_t seed, uint32_t stream_id, float *__restrict__ dqkv, uint32_t *__restrict__ row_scale,
@@ -792,7 +862,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
   const int q = q0 + l31, qc = min(q, L - 1);
   const bool q_ok = q < L;
   constexpr int KS = DK / 16, NT = DK / 32;
-  const float scale = DK == 64 ? 0.125f : 0.17677669529663687f;
+  const float scale = attn_scale<DK>();
   const AttnDrop dk_ = make_attn_drop(seed, stream_id, (uint32_t)(b * H + h), p_drop);
   const uint32_t q_part = attn_q_part(dk_, (uint32_t)q);
 
@@ -827,7 +897,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 
   Stage<DK, NW> stK[PARTS], stV[PARTS];
   const int ntiles = ((L + TR - 1) / TR + PARTS - 1) / PARTS;  // tiles of one part: part p walks tiles p ntiles ..
-  auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * BUF; };
+  constexpr int TE = HALVES<DK> * Tile2::ELEMS;  // f16 elements of one staged tile
+  auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * (HALVES<DK> * BUF); };
   // key mask of a tile as an ADDITIVE term of the soft-max argument (0 or -inf per key), read back one float4 per register
   // quadruple: no bit extraction and no select per element
   auto publish_mask = [&](int k0, int buf, int pt) __attribute__((always_inline)) {
@@ -845,7 +916,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
     stK[pt].load(base + D, toff);
     stV[pt].load(base + 2 * D, toff);
     stK[pt].store(tile(0, pt), sInvK[0][pt], pt * ntiles * TR, L, tid);
-    stV[pt].store(tile(0, pt) + Tile2::ELEMS, sInvV[0][pt], pt * ntiles * TR, L, tid);
+    stV[pt].store(tile(0, pt) + TE, sInvV[0][pt], pt * ntiles * TR, L, tid);
     publish_mask(pt * ntiles * TR, 0, pt);
     const auto toff2 = rows[pt].next();
     stK[pt].load(base + D, toff2);
@@ -856,7 +927,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
   for (int kt = 0; kt < ntiles; ++kt) {
     const int k0 = (part * ntiles + kt) * TR, cur = kt & 1;
     const bool more = kt + 1 < ntiles;
-    const unsigned short *sK = tile(cur, part), *sV = sK + Tile2::ELEMS;
+    const unsigned short *sK = tile(cur, part), *sV = sK + TE;
 #pragma unroll
     for (int pt = 0; pt < PARTS; ++pt) {
       const auto toff = rows[pt].next();
@@ -871,8 +942,13 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       f16x8 kf[2], vf[2];
-      Tile2::frag_rows(sK, st, lane, kf);
-      Tile2::frag_rows(sV, st, lane, vf);
+      if constexpr (HALVES<DK> == 1) {  // (dk = 64 / 32 written out: same instructions)
+        Tile2::frag_rows(sK, st, lane, kf);
+        Tile2::frag_rows(sV, st, lane, vf);
+      } else {
+        tile_frag_rows<Tile2>(sK, st, lane, kf);
+        tile_frag_rows<Tile2>(sV, st, lane, vf);
+      }
       s = mfma3(kf, qf[st], s);     // S^T[key][q]
       dp = mfma3(vf, gf[st], dp);   // dP^T[key][q] = V dO^T
     }
@@ -881,7 +957,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
       for (int pt = 0; pt < PARTS; ++pt) {
         const int kn = (pt * ntiles + kt + 1) * TR;
         stK[pt].store(tile(cur ^ 1, pt), sInvK[cur ^ 1][pt], kn, L, tid);
-        stV[pt].store(tile(cur ^ 1, pt) + Tile2::ELEMS, sInvV[cur ^ 1][pt], kn, L, tid);
+        stV[pt].store(tile(cur ^ 1, pt) + TE, sInvV[cur ^ 1][pt], kn, L, tid);
         publish_mask(kn, cur ^ 1, pt);
       }
     }
@@ -927,7 +1003,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         f16x8 kt_[2];
-        Tile2::frag_cols(sK, 16 * m, 32 * t, lane, kt_);
+        if constexpr (HALVES<DK> == 1) Tile2::frag_cols(sK, 16 * m, 32 * t, lane, kt_);
+        else tile_frag_cols<Tile2>(sK, 16 * m, t, lane, kt_);
         dq[t] = mfma3(kt_, df, dq[t]);
       }
     }
@@ -984,7 +1061,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 // BITS: the dropout decisions are the forward kernel's (keep_bits, one word per key and 32-query tile) - the generator is
 // not compiled in (as in attn_bwd_fused_f16x2_kernel below)
 template <int DK, int NW, int PARTS, bool BITS>
-__global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dkv_f16x2_kernel(
+__global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_WAVES<DK>, BWD_WAVES<DK>))) void attn_bwd_dkv_f16x2_kernel(
     const float *__restrict__ qkv, const int64_t *__restrict__ seq, const float *__restrict__ d_o,
     const float *__restrict__ lse, const float *__restrict__ delta, int L, int H, float p_drop, uint64_t seed,
     uint32_t stream_id, float *__restrict__ dqkv, uint32_t *__restrict__ row_scale, uint32_t *__restrict__ row_min,
@@ -1005,7 +1082,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
   const bool k_ok = key < L;
   const bool k_valid = k_ok && seq[(size_t)b * L + key] != PTAMD_PAD_ID;
   constexpr int KS = DK / 16, NT = DK / 32;
-  const float scale = DK == 64 ? 0.125f : 0.17677669529663687f;
+  const float scale = attn_scale<DK>();
   const int lkb = (L + 31) & ~31;   // keys (and query tiles x 32) of the keep_bits layout
   const AttnDrop dk_ = make_attn_drop(seed, stream_id, (uint32_t)(b * H + h), p_drop);
   const float ks = p_drop > 0.f ? dk_.ks : 1.f;
@@ -1025,10 +1102,14 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 
   Stage<DK, NW> stQ[PARTS], stG[PARTS];
   const int ntiles = ((L + TR - 1) / TR + PARTS - 1) / PARTS;  // query tiles of one part: part p walks tiles p ntiles ..
-  auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * BUF; };
+  constexpr int TE = HALVES<DK> * Tile2::ELEMS;  // f16 elements of one staged tile
+  auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * (HALVES<DK> * BUF); };
   float r_lse[PARTS], r_del[PARTS];
   TileRows<DK, NW> rows_q[PARTS], rows_g[PARTS];
   Stage<DK, NW> nxQ[PARTS], nxG[PARTS];
+  // loads run two tiles ahead of the arithmetic; one tile ahead at head size 128, whose K and V operands fill half the
+  // register file (two staged tiles more are 32 registers: spilled)
+  constexpr bool AHEAD2 = HALVES<DK> == 1;
 #pragma unroll
   for (int pt = 0; pt < PARTS; ++pt) {
     const int first = pt * ntiles * TR;
@@ -1037,25 +1118,32 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
     stQ[pt].load(base, rows_q[pt].next());
     stG[pt].load(gbase, rows_g[pt].next());
     stQ[pt].store(tile(0, pt), sInvQ[0][pt], first, L, tid);
-    stG[pt].store(tile(0, pt) + Tile2::ELEMS, sInvG[0][pt], first, L, tid);
+    stG[pt].store(tile(0, pt) + TE, sInvG[0][pt], first, L, tid);
     r_lse[pt] = r_del[pt] = 0.f;
     if (tid < TR) {
       sLse[0][pt][tid] = first + tid < L ? lse_b[first + tid] * LOG2E : INFINITY;
       sDel[0][pt][tid] = first + tid < L ? del_b[first + tid] : 0.f;
     }
-    stQ[pt].load(base, rows_q[pt].next());
-    stG[pt].load(gbase, rows_g[pt].next());
+    if constexpr (AHEAD2) {
+      stQ[pt].load(base, rows_q[pt].next());
+      stG[pt].load(gbase, rows_g[pt].next());
+    }
   }
   __syncthreads();
 
   for (int qt = 0; qt < ntiles; ++qt) {
     const int qq0 = (part * ntiles + qt) * TR, cur = qt & 1;
     const bool more = qt + 1 < ntiles;
-    const unsigned short *sQ = tile(cur, part), *sG = sQ + Tile2::ELEMS;
+    const unsigned short *sQ = tile(cur, part), *sG = sQ + TE;
 #pragma unroll
     for (int pt = 0; pt < PARTS; ++pt) {
-      nxQ[pt].load(base, rows_q[pt].next());
-      nxG[pt].load(gbase, rows_g[pt].next());
+      if constexpr (AHEAD2) {
+        nxQ[pt].load(base, rows_q[pt].next());
+        nxG[pt].load(gbase, rows_g[pt].next());
+      } else {
+        stQ[pt].load(base, rows_q[pt].next());
+        stG[pt].load(gbase, rows_g[pt].next());
+      }
       if (more && tid < TR) {
         const int qn = (pt * ntiles + qt + 1) * TR + tid;
         r_lse[pt] = qn < L ? lse_b[qn] * LOG2E : INFINITY;
@@ -1073,8 +1161,13 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       f16x8 qa[2], ga[2];
-      Tile2::frag_rows(sQ, st, lane, qa);
-      Tile2::frag_rows(sG, st, lane, ga);
+      if constexpr (HALVES<DK> == 1) {
+        Tile2::frag_rows(sQ, st, lane, qa);
+        Tile2::frag_rows(sG, st, lane, ga);
+      } else {
+        tile_frag_rows<Tile2>(sQ, st, lane, qa);
+        tile_frag_rows<Tile2>(sG, st, lane, ga);
+      }
       s = mfma3(qa, kf[st], s);     // S[q][key]
       dp = mfma3(ga, vf[st], dp);   // dP[q][key] = dO V^T
     }
@@ -1083,7 +1176,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
       for (int pt = 0; pt < PARTS; ++pt) {
         const int qn = (pt * ntiles + qt + 1) * TR;
         stQ[pt].store(tile(cur ^ 1, pt), sInvQ[cur ^ 1][pt], qn, L, tid);
-        stG[pt].store(tile(cur ^ 1, pt) + Tile2::ELEMS, sInvG[cur ^ 1][pt], qn, L, tid);
+        stG[pt].store(tile(cur ^ 1, pt) + TE, sInvG[cur ^ 1][pt], qn, L, tid);
         if (tid < TR) {
           sLse[cur ^ 1][pt][tid] = r_lse[pt];
           sDel[cur ^ 1][pt][tid] = r_del[pt];
@@ -1167,16 +1260,20 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         f16x8 qt_[2], gt_[2];
-        Tile2::frag_cols(sQ, 16 * m, 32 * t, lane, qt_);
+        if constexpr (HALVES<DK> == 1) Tile2::frag_cols(sQ, 16 * m, 32 * t, lane, qt_);
+        else tile_frag_cols<Tile2>(sQ, 16 * m, t, lane, qt_);
         dk[t] = mfma3(qt_, dsf, dk[t]);   // dK^T[d][key] += Q^T dS
-        Tile2::frag_cols(sG, 16 * m, 32 * t, lane, gt_);
+        if constexpr (HALVES<DK> == 1) Tile2::frag_cols(sG, 16 * m, 32 * t, lane, gt_);
+        else tile_frag_cols<Tile2>(sG, 16 * m, t, lane, gt_);
         dv[t] = mfma3(gt_, pdf, dv[t]);   // dV^T[d][key] += dO^T Pd
       }
     }
 #pragma unroll
     for (int pt = 0; pt < PARTS; ++pt) {
-      stQ[pt] = nxQ[pt];
-      stG[pt] = nxG[pt];
+      if constexpr (AHEAD2) {
+        stQ[pt] = nxQ[pt];
+        stG[pt] = nxG[pt];
+      }
     }
     __syncthreads();
   }
@@ -1731,7 +1828,8 @@ enum Bwd { BWD_TWO_KERNELS, BWD_SWEEP, BWD_SPLIT };
 // Every kernel choice of one (B, L, H, dk): the forward pass, the backward pass and the workspace and K / V plane queries
 // all read it, so they cannot disagree.
 struct Plan {
-  Shape shape;      // forward and dQ kernels: W8, W8_HALVES or W4_HALVES (dkv_shape: the dK/dV kernel)
+  Shape shape;      // forward and dQ kernels: W8, W8_HALVES or W4_HALVES (dkv_shape: the dK/dV kernel); head size 128:
+                    // W8 or W4 for the forward kernel, the backward kernels always W4
   bool quarters;    // forward: 2 query groups x 4 key quarters in place of W4_HALVES
   Bwd bwd;
   int nkb, qs;      // split sweep: 256-key blocks, query ranges
@@ -1740,6 +1838,15 @@ struct Plan {
 inline Plan plan(int B, int L, int H, int dk) {
   const size_t cus = (size_t)ptgemm::persistent_grid(0), bh = (size_t)H * B;
   Plan pl;
+  if (dk == 128) {  // W8 or W4 forward (no room for two halves of the keys), the two-kernel backward at 4 wavefronts
+    pl.shape = (size_t)((L + 255) / 256) * bh * 2 > cus ? W8 : W4;
+    pl.quarters = false;
+    pl.bwd = BWD_TWO_KERNELS;
+    pl.nkb = (L + FK - 1) / FK;
+    pl.qs = 1;
+    pl.kv_planes = false;
+    return pl;
+  }
   if ((size_t)((L + 255) / 256) * bh * 2 > cus) pl.shape = W8;
   else pl.shape = (size_t)((L + 127) / 128) * bh * 2 > cus ? W8_HALVES : W4_HALVES;
   // the 2 x 4 forward shape where the key range has a tile for every quarter
@@ -1777,9 +1884,10 @@ int launch_fwd(const float *qkv, const int64_t *seq, int B, int L, int H, float 
                float *lse, uint32_t *keep_bits, hipStream_t st) {
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
-  if (int rc = set_lds(attn_fwd_f16x2_kernel<DK, NW, PARTS>, PARTS * ATTN_LDS)) return rc;
-  hipLaunchKernelGGL((attn_fwd_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, L, H, p, seed, sid,
-                     out, lse, keep_bits);
+  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
+  if (int rc = set_lds(attn_fwd_f16x2_kernel<DK, NW, PARTS>, LDS)) return rc;
+  hipLaunchKernelGGL((attn_fwd_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), LDS, st, qkv, seq, L, H, p, seed, sid, out, lse,
+                     keep_bits);
   return pt_check_launch();
 }
 // 8 wavefronts as 2 query groups x 4 key quarters on unpadded tiles (round 6; head size 64): as many workgroups as 4 x (2 x 2)
@@ -1799,8 +1907,9 @@ int launch_dq(const float *qkv, const int64_t *seq, const float *o_fwd, const fl
               hipStream_t st) {
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
-  if (int rc = set_lds(attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>, PARTS * ATTN_LDS)) return rc;
-  hipLaunchKernelGGL((attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, o_fwd, d_o, lse,
+  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
+  if (int rc = set_lds(attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>, LDS)) return rc;
+  hipLaunchKernelGGL((attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), LDS, st, qkv, seq, o_fwd, d_o, lse,
                      delta, L, H, p, seed, sid, dqkv, row_scale, row_min);
   return pt_check_launch();
 }
@@ -1810,13 +1919,14 @@ int launch_dkv(const float *qkv, const int64_t *seq, const float *d_o, const flo
                hipStream_t st) {
   constexpr int QB = 32 * NW / PARTS;
   const dim3 grid((L + QB - 1) / QB, H, B);
+  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
   if (keep_bits && p > 0.f) {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>, PARTS * ATTN_LDS)) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, d_o, lse,
+    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>, LDS)) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>), grid, dim3(64 * NW), LDS, st, qkv, seq, d_o, lse,
                        delta, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits);
   } else {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>, PARTS * ATTN_LDS)) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>), grid, dim3(64 * NW), PARTS * ATTN_LDS, st, qkv, seq, d_o, lse,
+    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>, LDS)) return rc;
+    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>), grid, dim3(64 * NW), LDS, st, qkv, seq, d_o, lse,
                        delta, L, H, p, seed, sid, dqkv, row_scale, row_min, nullptr);
   }
   return pt_check_launch();
@@ -1832,9 +1942,13 @@ template <int DK>
 int fwd_by_plan(const Plan &pl, const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
                 float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
   if (pl.shape == W8) return launch_fwd<DK, 8, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  if (pl.shape == W8_HALVES) return launch_fwd<DK, 8, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  if (pl.quarters) return launch_fwd_quarters(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  return launch_fwd<DK, 4, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  if constexpr (DK == 128) {  // W4
+    return launch_fwd<DK, 4, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  } else {
+    if (pl.shape == W8_HALVES) return launch_fwd<DK, 8, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+    if (pl.quarters) return launch_fwd_quarters(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+    return launch_fwd<DK, 4, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+  }
 }
 int launch_fused_split(const Plan &pl, const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o,
                        const float *lse, float *delta, float *slabs, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
@@ -1905,12 +2019,15 @@ int pt_attention_fwd_f16x2(const float *qkv, const int64_t *seq, int B, int L, i
     if (!kv_inv || !pl.kv_planes) return PTAMD_ERR_BAD_SHAPE;
     return launch_fwd_kvp(qkv, static_cast<const char *>(kv_planes), kv_inv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
   }
+  if (dk == 128) return fwd_by_plan<128>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
   return dk == 64 ? fwd_by_plan<64>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st)
                   : fwd_by_plan<32>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
 }
 
 // (the one-sweep kernel and, on the two-kernel path, the dK / dV kernel - both keep keys in lanes; the dQ kernel draws them)
-bool pt_attention_bwd_f16x2_reads_keep_bits(int B, int L, int H, int dk) { return B > 0 && L > 0 && H > 0 && (dk == 64 || dk == 32); }
+bool pt_attention_bwd_f16x2_reads_keep_bits(int B, int L, int H, int dk) {
+  return B > 0 && L > 0 && H > 0 && (dk == 64 || dk == 32 || dk == 128);
+}
 
 // floats of workspace the f16x2 backward pass of this shape wants BEHIND delta (the slabs of the split sweep; 0 otherwise)
 size_t pt_attention_bwd_f16x2_slab_floats(int B, int L, int H, int dk) {
@@ -1934,6 +2051,11 @@ int pt_attention_bwd_f16x2(const float *qkv, const int64_t *seq, const float *o_
     if (!slabs || slab_floats < split_floats(B, L, H, pl)) return PTAMD_ERR_WORKSPACE;
     return launch_fused_split(pl, qkv, seq, o_fwd, d_o, lse, delta, slabs, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
                               static_cast<const char *>(kv_planes), kv_inv, st);
+  }
+  if (dk == 128) {  // (W4 for both kernels whatever the forward shape)
+    const int rc = launch_dq<128, 4, 1>(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, st);
+    if (rc) return rc;
+    return launch_dkv<128, 4, 1>(qkv, seq, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
   }
   return dk == 64 ? bwd_by_shape<64>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st)
                   : bwd_by_shape<32>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);

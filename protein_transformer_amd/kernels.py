@@ -534,7 +534,7 @@ def attention_bwd_reads_keep_bits(B, L, H, dk, arith):
 
 
 def attention_keep_bits(B, L, H, device):
-    """Buffer for the dropout decisions ptamd_attention_fwd hands to ptamd_attention_bwd (f16x2 arithmetic, dk 32 / 64)."""
+    """Buffer for the dropout decisions ptamd_attention_fwd hands to ptamd_attention_bwd (f16x2 arithmetic, dk 32 / 64 / 128)."""
     return torch.empty(lib().ptamd_attention_keep_bits_bytes(B, L, H) // 4, dtype=torch.int32, device=device)
 
 
@@ -566,7 +566,7 @@ def attention_fwd(qkv, seq, H, dropout_p, seed, stream_id, arith=None, keep_bits
 def attention_bwd(qkv, seq, out, dout, lse, H, dropout_p, seed, stream_id, arith=None, row_scale=None, row_scale_min=None,
                   keep_bits=None, kv=None):
     """row_scale [T] / row_scale_min [4] (int32, preset to 0x7F000000): f16x2 scales of the rows of dqkv as a by-product
-    (f16x2 arithmetic and head size 32 / 64 only - `attention_row_scales_available`).  keep_bits: what attention_fwd filled
+    (f16x2 arithmetic and head size 32 / 64 / 128 only - `attention_row_scales_available`).  keep_bits: what attention_fwd filled
     for the same (seed, stream_id) - the fused backward kernel reads the decisions instead of drawing them again."""
     B, L = seq.shape
     D = qkv.shape[1] // 3
@@ -581,7 +581,7 @@ def attention_bwd(qkv, seq, out, dout, lse, H, dropout_p, seed, stream_id, arith
 
 
 def attention_row_scales_available(dk, arith):
-    return dk in (32, 64) and int(arith) in (GEMM_AUTO, GEMM_F16X2)
+    return dk in (32, 64, 128) and int(arith) in (GEMM_AUTO, GEMM_F16X2)
 
 
 def relu_dropout_bwd(dy, y, dropout_p):

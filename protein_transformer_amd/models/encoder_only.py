@@ -309,8 +309,8 @@ class _TransformerBase(nn.Module):
         D = self.dlayer
         assert D % nhead == 0, "The dimension of the model must be evenly divisible by the number of attn heads."
         widths = [dmodel, D, dff] + [c for _, c, _ in (self.conv_shapes or [])]
-        if any(w % 4 for w in widths) or (D // nhead) not in (8, 16, 32, 64):
-            raise ValueError("libptamd needs channel widths that are multiples of 4 and width / n_head in {8, 16, 32, 64}")
+        if any(w % 4 for w in widths) or (D // nhead) not in (8, 16, 32, 64, 128):
+            raise ValueError("libptamd needs channel widths that are multiples of 4 and width / n_head in {8, 16, 32, 64, 128}")
         self.encoder = _EncoderHolder(len(vocab), dmodel, D, dff, nlayers, max_seq_len, self.conv_shapes,
                                       self.use_embedding)
         self.output_projection = _Holder(weight=(NUM_PREDICTED_ANGLES * 2, D), bias=(NUM_PREDICTED_ANGLES * 2,))
