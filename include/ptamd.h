@@ -78,6 +78,18 @@ int ptamd_nerf_fwd(const float *ang, const int64_t *seq, int B, int L, float *cr
  * reference's graph: first residue's C is detached (StructureBuilder.py:185-187). */
 int ptamd_nerf_bwd(const float *ang, const int64_t *seq, const float *crd, const float *dcrd, int B, int L,
                    float *dang, void *workspace, size_t workspace_bytes, void *stream);
+/* The backbone alone, for the backbone-only loss (losses.py:83-92 with backbone_only = True, i.e. train.py --backbone_loss;
+ * get_backbone_from_full_coords, structure_utils.py:19-32): the chain of ResidueBuilder.build_bb (StructureBuilder.py:147-191)
+ * WITHOUT the O and side-chain placements of build_sc.
+ *   crd_bb [B,L*3,3] out: N, CA, C of every residue, COMPACT (3 atoms per residue, not the 14-slot layout; padded residues and
+ *   proteins of fewer than two residues = 0) - bit for bit slots 0..2 of what ptamd_nerf_fwd writes (same one-wavefront scan,
+ *   same composition order); status as for ptamd_nerf_fwd.  One launch. */
+int ptamd_nerf_bb_fwd(const float *ang, const int64_t *seq, int B, int L, float *crd_bb, int32_t *status, void *stream);
+/* its adjoint: dcrd_bb [B,L*3,3] -> dang [B,L,12], ALL 12 channels written (exact zeros where nothing flows: the six side-chain
+ * torsions, padded residues, and what the reference's graph leaves out - first residue's C detached, StructureBuilder.py:185-187,
+ * the last residue's psi / omega / CA-C-N / C-N-CA); no workspace, no fill in front.  One launch. */
+int ptamd_nerf_bb_bwd(const float *ang, const int64_t *seq, const float *crd_bb, const float *dcrd_bb, int B, int L,
+                      float *dang, void *stream);
 
 /* ------------------------------------------------------------------ dRMSD
  * drmsd_work's loss part for a whole batch (losses.py:63-92,233-278; structure_utils.py:19-32).
@@ -100,6 +112,25 @@ size_t ptamd_drmsd_workspace_bytes_budget(int B, int L, size_t partial_budget_by
 int ptamd_drmsd_fwd_bwd_budget(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L,
                                float *stats, float *dcrd, void *workspace, size_t workspace_bytes,
                                size_t partial_budget_bytes, void *stream);
+/* The backbone-only loss (losses.py:83-92: drmsd over get_backbone_from_full_coords of both structures, structure_utils.py:19-32,
+ * and the gradient of its length-normalised form): the same compaction, upper-triangle sweep and finalisation over the present
+ * N, CA, C alone.
+ *   pred_bb [B,L*3,3]: the COMPACT backbone of ptamd_nerf_bb_fwd (predicted coordinates travel between the two kernels in this
+ *   layout: there are no side-chain slots to leave unwritten); true_crd [B,L*14,3] as above - only its slots s % 14 < 3 are read,
+ *   NaN = atom absent.
+ *   stats [B,8] out, same layout: entries 2, 3, 5 = {bb_drmsd, bb_drmsd/n_bb, n_bb} - what ptamd_drmsd_fwd_bwd reports there -
+ *   and entries 0, 1, 4 MIRROR them.
+ *   dbb [B,L*3,3] out or NULL: d(bb_drmsd/n_bb)/d(pred_bb); a protein with fewer than two present backbone atoms gets zeros
+ *   (its statistics are NaN, the mean over an empty pair set, as in the reference).
+ * Workspace, tiles, strips, work items, partial sums and passes are those of the full sweep cut for n = 3 L atoms per protein
+ * instead of 14 L (B = 32, L = 512: 11.5 MiB against 158.6 MiB = 12.0e6 against 166.3e6 bytes); fixed-order partials, no atomics, passes give the bits of one launch. */
+size_t ptamd_drmsd_bb_workspace_bytes(int B, int L);
+int ptamd_drmsd_bb_fwd_bwd(const float *pred_bb, const float *true_crd, const int64_t *seq, int B, int L,
+                           float *stats, float *dbb, void *workspace, size_t workspace_bytes, void *stream);
+size_t ptamd_drmsd_bb_workspace_bytes_budget(int B, int L, size_t partial_budget_bytes);
+int ptamd_drmsd_bb_fwd_bwd_budget(const float *pred_bb, const float *true_crd, const int64_t *seq, int B, int L,
+                                  float *stats, float *dbb, void *workspace, size_t workspace_bytes,
+                                  size_t partial_budget_bytes, void *stream);
 
 /* rmsd (losses.py:281-286, ProDy calcTransformation + calcRMSD) for a whole batch: RMSD of the predicted atoms after optimal
  * rigid superposition (Kabsch) onto the true ones, over the atoms whose truth is present (NaN = absent), residues with

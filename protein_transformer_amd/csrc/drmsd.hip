@@ -61,6 +61,13 @@ __device__ int protein_len_block(const int64_t *seq, int L, int *s_tmp) {
 // no workgroup barrier inside the loops, so the loads of consecutive rows overlap (the old per-thread runs of 28 slots
 // were 2 x 28 dependent strided loads: 46 us whatever the batch).  Order inside the two classes: slot order.
 constexpr int COMPACT_THREADS = 1024;  // 16 wavefronts: 7 rows of 64 slots each at L = 512
+// SPR = atom slots per residue of `pred` and of everything behind the compaction.  14: every atom.  3: the backbone-only loss
+// (losses.py:83-92 with backbone_only, structure_utils.py:19-32) - `pred` is the COMPACT array [B, 3 L, 3] (N, CA, C per residue,
+// as ptamd_nerf_bb_fwd writes it), `truth` stays [B, 14 L, 3] and only its slots s % 14 < 3 are read; every atom is a backbone
+// atom (n == n_bb: the statistics of the whole set mirror the backbone's), idx = index into the compact array; buffers, tiles,
+// strips and work items behind it are cut for 3 L atoms per protein.
+constexpr int BB_SLOTS = 3, FULL_SLOTS = 14;
+template <int SPR>
 __global__ __launch_bounds__(COMPACT_THREADS) void drmsd_compact_kernel(const float *__restrict__ pred,
                                                            const float *__restrict__ truth,
                                                            const int64_t *__restrict__ seq, int L,
@@ -69,18 +76,19 @@ __global__ __launch_bounds__(COMPACT_THREADS) void drmsd_compact_kernel(const fl
   constexpr int NWAVE = COMPACT_THREADS / 64;
   __shared__ int s_bb[NWAVE], s_ot[NWAVE], s_tmp[NWAVE];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const size_t nmax = (size_t)L * 14;
+  const size_t nmax = (size_t)L * SPR;
   pred += (size_t)b * nmax * 3;
-  truth += (size_t)b * nmax * 3;
+  truth += (size_t)b * L * FULL_SLOTS * 3;
   pred4 += (size_t)b * nmax;
   col8 += (size_t)b * nmax;
   idx += (size_t)b * nmax;
   const int len = protein_len_block(seq + (size_t)b * L, L, s_tmp);
-  const int nslot = len * 14;
+  const int nslot = len * SPR;
   const int per = ((nslot + NWAVE - 1) / NWAVE + 63) / 64 * 64;   // slots of a wavefront: whole rows of 64
   const int s0 = min(w * per, nslot), s1 = min(s0 + per, nslot);
   auto present = [&](int s, float &tx, float &ty, float &tz) __attribute__((always_inline)) {
-    const int sc = min(s, max(nslot - 1, 0));
+    int sc = min(s, max(nslot - 1, 0));
+    if (SPR == BB_SLOTS) sc = (sc / BB_SLOTS) * FULL_SLOTS + sc % BB_SLOTS;   // the atom's slot in the 14-per-residue truth
     tx = truth[sc * 3]; ty = truth[sc * 3 + 1]; tz = truth[sc * 3 + 2];
     return s < s1 && !(isnan(tx) || isnan(ty) || isnan(tz));
   };
@@ -88,7 +96,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void drmsd_compact_kernel(const fl
   for (int r = s0; r < s1; r += 64) {
     float tx, ty, tz;
     const int s = r + lane;
-    const bool ok = present(s, tx, ty, tz), bb = (s % 14) < 3;
+    const bool ok = present(s, tx, ty, tz), bb = SPR == BB_SLOTS || (s % 14) < 3;
     nbb += __popcll(__ballot(ok && bb));
     not_ += __popcll(__ballot(ok && !bb));
   }
@@ -111,7 +119,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void drmsd_compact_kernel(const fl
   for (int r = s0; r < s1; r += 64) {
     float tx, ty, tz;
     const int s = r + lane;
-    const bool ok = present(s, tx, ty, tz), bb = (s % 14) < 3;
+    const bool ok = present(s, tx, ty, tz), bb = SPR == BB_SLOTS || (s % 14) < 3;
     const unsigned long long mb = __ballot(ok && bb), mo = __ballot(ok && !bb);
     const unsigned long long below = (1ull << lane) - 1ull;
     if (ok) {
@@ -192,7 +200,8 @@ __device__ __forceinline__ void colsum_rows(float4 &q, const float *__restrict__
   (colsum_row<R>(q, cf_q, px, py, pz), ...);
 }
 
-template <bool WITH_GRAD>
+// SPR = atom slots per residue of the arrays behind the compaction: 14 (every atom) or 3 (the backbone-only loss)
+template <bool WITH_GRAD, int SPR>
 __global__ __launch_bounds__(RS) void drmsd_tri_kernel(const Col8 *__restrict__ col8,
                                                        const Counts *__restrict__ counts, int L,
                                                        float4 *__restrict__ rowpart, float4 *__restrict__ colpart,
@@ -202,7 +211,7 @@ __global__ __launch_bounds__(RS) void drmsd_tri_kernel(const Col8 *__restrict__ 
   float4 *const s_cs = reinterpret_cast<float4 *>(s_dyn + STRIP_TILES * TS * CF_LD);   // [2][4][64] (S, Vx, Vy, Vz) per wavefront, two column tiles
   __shared__ double s_red[2 * STRIP_TILES];
   __shared__ Col8 s_col[2][TS];   // the column tile (all four wavefronts walk the same one), two buffers
-  const size_t nmax = (size_t)L * 14;
+  const size_t nmax = (size_t)L * SPR;
   const TriLayout tl = tri_layout((int)nmax, (int)gridDim.y);
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // (told to the compiler: what depends on w only stays scalar)
@@ -441,6 +450,7 @@ __device__ __forceinline__ void gather_partials(const TriLayout &tl, int b, int 
 }
 
 // between the passes of a long batch: the running (row sum, column sum) of every atom, grid (ceil(nmax / 256), B)
+template <int SPR>
 __global__ __launch_bounds__(CB) void drmsd_accumulate_kernel(const Counts *__restrict__ counts, const float4 *__restrict__ pred4,
                                                               const float4 *__restrict__ rowpart, const float4 *__restrict__ colpart,
                                                               int L, int strip0, int spp, float4 *__restrict__ grow,
@@ -448,7 +458,7 @@ __global__ __launch_bounds__(CB) void drmsd_accumulate_kernel(const Counts *__re
   const int b = blockIdx.y, j = blockIdx.x * CB + threadIdx.x;
   const Counts cn = counts[b];
   if (j >= cn.n) return;
-  const size_t nmax = (size_t)L * 14;
+  const size_t nmax = (size_t)L * SPR;
   const TriLayout tl = tri_layout((int)nmax, (int)gridDim.y);
   const size_t at = (size_t)b * nmax + j;
   RowCol g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -463,6 +473,7 @@ __global__ __launch_bounds__(CB) void drmsd_accumulate_kernel(const Counts *__re
 
 // statistics, gradient assembly and scatter back to the slot layout: grid (ceil(nmax / 256), B); dcrd was zeroed before.
 // grow / gcol != nullptr: the sweep ran in passes and drmsd_accumulate_kernel has already summed the partials.
+template <int SPR>
 __global__ __launch_bounds__(CB) void drmsd_finalize_kernel(const Counts *__restrict__ counts,
                                                             const double *__restrict__ partials,
                                                             const float4 *__restrict__ pred4,
@@ -474,7 +485,7 @@ __global__ __launch_bounds__(CB) void drmsd_finalize_kernel(const Counts *__rest
   __shared__ float s_scale;
   const int b = blockIdx.y, tid = threadIdx.x;
   const Counts cn = counts[b];
-  const size_t nmax = (size_t)L * 14;
+  const size_t nmax = (size_t)L * SPR;
   const TriLayout tl = tri_layout((int)nmax, (int)gridDim.y);
   if ((int)blockIdx.x * CB >= max(cn.n, 1)) return;
   // the work items' loss partials: every thread adds its share in item order, then a fixed tree over the threads (every
@@ -517,7 +528,9 @@ __global__ __launch_bounds__(CB) void drmsd_finalize_kernel(const Counts *__rest
       st[6] = 0.f;
       st[7] = 0.f;
     }
-    s_scale = (float)(1.0 / (n * P * (double)D));
+    // backbone-only loss: fewer than two present atoms = no pair - the protein contributes a zero gradient (its statistics are
+    // the NaN of a mean over an empty set, as in the reference)
+    s_scale = (SPR == BB_SLOTS && cn.n < 2) ? 0.f : (float)(1.0 / (n * P * (double)D));
   }
   if (dcrd == nullptr) return;
   __syncthreads();
@@ -550,9 +563,9 @@ struct Layout {
   int spp;   // strips per pass (= strips: one launch)
   TriLayout tl;
 };
-Layout layout(int B, int L, size_t budget) {
+Layout layout(int B, int L, size_t budget, int spr = FULL_SLOTS) {   // spr: atom slots per residue (14, or 3: backbone only)
   Layout l;
-  const size_t nmax = (size_t)L * 14, BN = (size_t)B * nmax;
+  const size_t nmax = (size_t)L * spr, BN = (size_t)B * nmax;
   l.tl = tri_layout((int)nmax, B);
   if (budget == 0) budget = PARTIAL_BUDGET;
   const size_t per_strip = (size_t)B * ((size_t)l.tl.chunks * RS + (size_t)l.tl.tiles * TS) * sizeof(float4);
@@ -578,6 +591,50 @@ Layout layout(int B, int L, size_t budget) {
   return l;
 }
 
+// compaction, pair sweep (in passes beyond the budget), finalisation: SPR = 14 for [B, 14 L, 3] predicted coordinates (every
+// atom), SPR = 3 for the compact [B, 3 L, 3] of the backbone-only loss; dcrd has the layout of pred_crd
+template <int SPR>
+int drmsd_run(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *stats, float *dcrd,
+              void *workspace, size_t workspace_bytes, size_t partial_budget_bytes, void *stream) {
+  if (B <= 0 || L <= 0) return PTAMD_ERR_BAD_SHAPE;
+  const Layout l = layout(B, L, partial_budget_bytes, SPR);
+  if (!workspace || workspace_bytes < l.total) return PTAMD_ERR_WORKSPACE;
+  if (!pt_aligned16(workspace)) return PTAMD_ERR_ALIGN;
+  char *ws = static_cast<char *>(workspace);
+  Col8 *col8 = reinterpret_cast<Col8 *>(ws + l.col8);
+  float4 *pred4 = reinterpret_cast<float4 *>(ws + l.pred4),
+         *rowpart = reinterpret_cast<float4 *>(ws + l.rowpart), *colpart = reinterpret_cast<float4 *>(ws + l.colpart);
+  int *idx = reinterpret_cast<int *>(ws + l.idx);
+  Counts *counts = reinterpret_cast<Counts *>(ws + l.counts);
+  double *partials = reinterpret_cast<double *>(ws + l.partials);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(drmsd_compact_kernel<SPR>, dim3(B), dim3(COMPACT_THREADS), 0, st,
+                     pred_crd, true_crd, seq, L, pred4, col8, idx, counts);
+  int rc = pt_check_launch();
+  if (rc) return rc;
+  const bool passes = l.spp < l.tl.strips;
+  float4 *grow = passes ? reinterpret_cast<float4 *>(ws + l.grow) : nullptr, *gcol = passes ? reinterpret_cast<float4 *>(ws + l.gcol) : nullptr;
+  const dim3 fin_grid((unsigned)(((size_t)L * SPR + CB - 1) / CB), B);
+  if (dcrd) PT_HIP_TRY(hipMemsetAsync(dcrd, 0, (size_t)B * L * SPR * 3 * sizeof(float), st));   // slots of absent atoms stay 0
+  auto kern = dcrd ? drmsd_tri_kernel<true, SPR> : drmsd_tri_kernel<false, SPR>;
+  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRI_LDS));
+  for (int s0 = 0; s0 < l.tl.strips; s0 += l.spp) {
+    const int ns = l.tl.strips - s0 < l.spp ? l.tl.strips - s0 : l.spp;
+    hipLaunchKernelGGL(kern, dim3(ns * l.tl.chunks, B), dim3(RS), TRI_LDS, st, col8, counts, L, rowpart, colpart, partials, s0, l.spp);
+    rc = pt_check_launch();
+    if (rc) return rc;
+    if (passes && dcrd) {
+      hipLaunchKernelGGL(drmsd_accumulate_kernel<SPR>, fin_grid, dim3(CB), 0, st, counts, pred4, rowpart, colpart, L, s0, l.spp,
+                         grow, gcol);
+      rc = pt_check_launch();
+      if (rc) return rc;
+    }
+  }
+  hipLaunchKernelGGL(drmsd_finalize_kernel<SPR>, fin_grid, dim3(CB), 0, st, counts, partials, pred4, rowpart, colpart,
+                     dcrd ? grow : nullptr, dcrd ? gcol : nullptr, idx, L, stats, dcrd);
+  return pt_check_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -595,43 +652,24 @@ int ptamd_drmsd_fwd_bwd(const float *pred_crd, const float *true_crd, const int6
 
 int ptamd_drmsd_fwd_bwd_budget(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *stats,
                                float *dcrd, void *workspace, size_t workspace_bytes, size_t partial_budget_bytes, void *stream) {
-  if (B <= 0 || L <= 0) return PTAMD_ERR_BAD_SHAPE;
-  const Layout l = layout(B, L, partial_budget_bytes);
-  if (!workspace || workspace_bytes < l.total) return PTAMD_ERR_WORKSPACE;
-  if (!pt_aligned16(workspace)) return PTAMD_ERR_ALIGN;
-  char *ws = static_cast<char *>(workspace);
-  Col8 *col8 = reinterpret_cast<Col8 *>(ws + l.col8);
-  float4 *pred4 = reinterpret_cast<float4 *>(ws + l.pred4),
-         *rowpart = reinterpret_cast<float4 *>(ws + l.rowpart), *colpart = reinterpret_cast<float4 *>(ws + l.colpart);
-  int *idx = reinterpret_cast<int *>(ws + l.idx);
-  Counts *counts = reinterpret_cast<Counts *>(ws + l.counts);
-  double *partials = reinterpret_cast<double *>(ws + l.partials);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(drmsd_compact_kernel, dim3(B), dim3(COMPACT_THREADS), 0, st, pred_crd, true_crd, seq, L, pred4, col8, idx,
-                     counts);
-  int rc = pt_check_launch();
-  if (rc) return rc;
-  const bool passes = l.spp < l.tl.strips;
-  float4 *grow = passes ? reinterpret_cast<float4 *>(ws + l.grow) : nullptr, *gcol = passes ? reinterpret_cast<float4 *>(ws + l.gcol) : nullptr;
-  const dim3 fin_grid((unsigned)(((size_t)L * 14 + CB - 1) / CB), B);
-  if (dcrd) PT_HIP_TRY(hipMemsetAsync(dcrd, 0, (size_t)B * L * 14 * 3 * sizeof(float), st));   // slots of absent atoms stay 0
-  auto kern = dcrd ? drmsd_tri_kernel<true> : drmsd_tri_kernel<false>;
-  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRI_LDS));
-  for (int s0 = 0; s0 < l.tl.strips; s0 += l.spp) {
-    const int ns = l.tl.strips - s0 < l.spp ? l.tl.strips - s0 : l.spp;
-    hipLaunchKernelGGL(kern, dim3(ns * l.tl.chunks, B), dim3(RS), TRI_LDS, st, col8, counts, L, rowpart, colpart, partials, s0, l.spp);
-    rc = pt_check_launch();
-    if (rc) return rc;
-    if (passes && dcrd) {
-      hipLaunchKernelGGL(drmsd_accumulate_kernel, fin_grid, dim3(CB), 0, st, counts, pred4, rowpart, colpart, L, s0, l.spp,
-                         grow, gcol);
-      rc = pt_check_launch();
-      if (rc) return rc;
-    }
-  }
-  hipLaunchKernelGGL(drmsd_finalize_kernel, fin_grid, dim3(CB), 0, st, counts, partials, pred4, rowpart, colpart,
-                     dcrd ? grow : nullptr, dcrd ? gcol : nullptr, idx, L, stats, dcrd);
-  return pt_check_launch();
+  return drmsd_run<FULL_SLOTS>(pred_crd, true_crd, seq, B, L, stats, dcrd, workspace, workspace_bytes, partial_budget_bytes, stream);
+}
+
+// backbone-only loss: the same sweep over the present N, CA, C alone, everything sized from 3 L atoms per protein
+size_t ptamd_drmsd_bb_workspace_bytes_budget(int B, int L, size_t partial_budget_bytes) {
+  if (B <= 0 || L <= 0) return 0;
+  return layout(B, L, partial_budget_bytes, BB_SLOTS).total;
+}
+size_t ptamd_drmsd_bb_workspace_bytes(int B, int L) { return ptamd_drmsd_bb_workspace_bytes_budget(B, L, 0); }
+
+int ptamd_drmsd_bb_fwd_bwd(const float *pred_bb, const float *true_crd, const int64_t *seq, int B, int L, float *stats,
+                           float *dbb, void *workspace, size_t workspace_bytes, void *stream) {
+  return ptamd_drmsd_bb_fwd_bwd_budget(pred_bb, true_crd, seq, B, L, stats, dbb, workspace, workspace_bytes, 0, stream);
+}
+
+int ptamd_drmsd_bb_fwd_bwd_budget(const float *pred_bb, const float *true_crd, const int64_t *seq, int B, int L, float *stats,
+                                  float *dbb, void *workspace, size_t workspace_bytes, size_t partial_budget_bytes, void *stream) {
+  return drmsd_run<BB_SLOTS>(pred_bb, true_crd, seq, B, L, stats, dbb, workspace, workspace_bytes, partial_budget_bytes, stream);
 }
 
 }  // extern "C"

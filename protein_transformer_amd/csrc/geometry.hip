@@ -197,7 +197,10 @@ __device__ __forceinline__ void placement_params(int p, int &res, int &col_th, i
 // grid = B, block = 64 NW (NW wavefronts per protein: round 6 - with one, 3 L = 1536 placements are 24 per lane and the
 // kernel takes 24.5 us whatever the batch; with four, 6 per lane, the wave-wide scans joined through LDS by at most three more
 // compositions).  dynamic LDS: chunk * 64 NW float4 of cached (sin th, cos th, sin chi, cos chi)
-template <int NW>
+// BB: the backbone-only build (ptamd_nerf_bb_fwd) - the same scan, same composition order, same bits, written to the COMPACT
+// array [B, 3 L, 3] (N, CA, C per residue: 9 floats instead of 42); no side-chain kernel follows, so the residues behind the
+// protein's end (all of them for a protein that is too short) are zeroed here
+template <int NW, bool BB>
 __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_fwd_kernel(const float *__restrict__ ang,
                                                                          const int64_t *__restrict__ seq, int L,
                                                                          float *__restrict__ crd,
@@ -209,11 +212,15 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_fwd_kernel(const f
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PT_WAVE - 1), wave = tid / PT_WAVE;
   ang += (size_t)b * L * 12;
   seq += (size_t)b * L;
-  crd += (size_t)b * L * 42;
+  constexpr int RES = BB ? 9 : 42;   // floats per residue of crd
+  crd += (size_t)b * L * RES;
   const int len = protein_len(seq, L, lane, status);   // (every wavefront counts: the same number, idempotent flags)
+  if (BB) {
+    for (int k = (len < 2 ? 0 : len * RES) + tid; k < L * RES; k += NT) crd[k] = 0.f;
+  }
   if (len < 2) {
     if (tid == 0) atomicOr(status, PTAMD_ST_TOO_SHORT);
-    return;  // the side-chain kernel zero-fills
+    return;  // the side-chain kernel zero-fills (BB: zeroed above)
   }
   const int K = 3 * (len - 1), chunk = (K + NT - 1) / NT;
   const int p0 = min(K, tid * chunk), p1 = min(K, p0 + chunk);
@@ -303,7 +310,7 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_fwd_kernel(const f
     const float4 tr = trig[(p - p0) * NT + tid];
     g = xf_mul(g, xf_local(l, tr.x, tr.y, tr.z, tr.w));
     const int i = 1 + p / 3;
-    float *o = crd + (size_t)i * 42 + slot * 3;
+    float *o = crd + (size_t)i * RES + slot * 3;
     o[0] = g.t[0];
     o[1] = g.t[1];
     o[2] = g.t[2];
@@ -511,8 +518,16 @@ __global__ __launch_bounds__(SC_BLOCK) void nerf_sidechain_bwd_kernel(const floa
 // reference differentiates with autograd; the graph quirks come for free: P_0..P_2 are constants (first C is
 // detached, StructureBuilder.py:185-187), so only placements k >= 3 receive gradients, and the last residue's
 // omega / CA-C-N / C-N-CA have nothing downstream.
+// BB (backbone-only adjoint): crd and gbb are the compact [3 L, 3] coordinates and their gradient - chain atom j at 3 j, nothing
+// hangs off the backbone
+template <bool BB>
 __device__ __forceinline__ void chain_atom(const float *__restrict__ crd, const float *__restrict__ gbb, int len, int j,
                                            V3 &P, V3 &g) {
+  if (BB) {
+    P = ld3(crd + (size_t)j * 3);
+    g = ld3(gbb + (size_t)j * 3);
+    return;
+  }
   const int i = j / 3, a = j - 3 * i;
   P = ld3(crd + (size_t)i * 42 + a * 3);
   g = ld3(gbb + (size_t)i * 12 + a * 3);
@@ -521,7 +536,9 @@ __device__ __forceinline__ void chain_atom(const float *__restrict__ crd, const 
 }
 
 // (NW wavefronts per protein, as in the forward kernel: the suffix sums of the later wavefronts come through LDS)
-template <int NW>
+// BB: gbb = dL/d(compact coordinates) itself; every channel of dang is written here (zeros where nothing flows: the side-chain
+// torsions, the channels the reference's graph leaves out), no kernel runs in front
+template <int NW, bool BB>
 __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const float *__restrict__ ang,
                                                                          const int64_t *__restrict__ seq,
                                                                          const float *__restrict__ crd,
@@ -532,11 +549,15 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const f
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PT_WAVE - 1), wave = tid / PT_WAVE;
   ang += (size_t)b * L * 12;
   seq += (size_t)b * L;
-  crd += (size_t)b * L * 42;
-  gbb += (size_t)b * L * 12;
+  crd += (size_t)b * L * (BB ? 9 : 42);
+  gbb += (size_t)b * L * (BB ? 9 : 12);
   dang += (size_t)b * L * 12;
   int32_t dummy = 0;
   const int len = protein_len(seq, L, lane, &dummy);
+  if (BB) {   // the zeros first, behind a barrier: an angle that receives a gradient is stored once more below, by another thread
+    for (int k = tid; k < L * 12; k += NT) dang[k] = 0.f;
+    __syncthreads();
+  }
   if (len < 2) return;
   const int n = 3 * len, chunk = (n + NT - 1) / NT;
   const int j0 = min(n, tid * chunk), j1 = min(n, j0 + chunk);
@@ -544,7 +565,7 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const f
   double F[3] = {0, 0, 0}, T[3] = {0, 0, 0};
   for (int j = j0; j < j1; ++j) {
     V3 P, g;
-    chain_atom(crd, gbb, len, j, P, g);
+    chain_atom<BB>(crd, gbb, len, j, P, g);
     F[0] += g.x; F[1] += g.y; F[2] += g.z;
     T[0] += (double)P.y * g.z - (double)P.z * g.y;
     T[1] += (double)P.z * g.x - (double)P.x * g.z;
@@ -587,7 +608,7 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const f
   }
   for (int j = j1 - 1; j >= j0; --j) {
     V3 P, g;
-    chain_atom(crd, gbb, len, j, P, g);
+    chain_atom<BB>(crd, gbb, len, j, P, g);
     F[0] += g.x; F[1] += g.y; F[2] += g.z;
     T[0] += (double)P.y * g.z - (double)P.z * g.y;
     T[1] += (double)P.z * g.x - (double)P.x * g.z;
@@ -597,9 +618,9 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const f
     float l;
     placement_params(j - 3, res, cth, cchi, l, slot);
     const int ia = (j - 3) / 3, ib = (j - 2) / 3, ic = (j - 1) / 3;
-    const V3 pa = ld3(crd + (size_t)ia * 42 + ((j - 3) - 3 * ia) * 3);
-    const V3 pb = ld3(crd + (size_t)ib * 42 + ((j - 2) - 3 * ib) * 3);
-    const V3 pc = ld3(crd + (size_t)ic * 42 + ((j - 1) - 3 * ic) * 3);
+    const V3 pa = ld3(BB ? crd + (size_t)(j - 3) * 3 : crd + (size_t)ia * 42 + ((j - 3) - 3 * ia) * 3);
+    const V3 pb = ld3(BB ? crd + (size_t)(j - 2) * 3 : crd + (size_t)ib * 42 + ((j - 2) - 3 * ib) * 3);
+    const V3 pc = ld3(BB ? crd + (size_t)(j - 1) * 3 : crd + (size_t)ic * 42 + ((j - 1) - 3 * ic) * 3);
     float n0, n1, n2;
     const V3 W = unit(pb - pa, n0), x = unit(pc - pb, n1);
     const V3 z = unit(cross(W, x), n2), y = cross(z, x);
@@ -612,7 +633,7 @@ __global__ __launch_bounds__(PT_WAVE * NW) void nerf_backbone_bwd_kernel(const f
     const float dchi = (float)(x.x * tq0 + x.y * tq1 + x.z * tq2);
     const float dth = (float)(ax.x * tq0 + ax.y * tq1 + ax.z * tq2);
     dang[res * 12 + cth] = dth;
-    if (cchi == 1) dang[res * 12 + 1] += dchi;  // psi also placed O (the side-chain kernel wrote that part)
+    if (!BB && cchi == 1) dang[res * 12 + 1] += dchi;  // psi also placed O (the side-chain kernel wrote that part)
     else dang[res * 12 + cchi] = dchi;
   }
 }
@@ -655,6 +676,21 @@ __global__ void pairwise_dist_kernel(const float *__restrict__ x, int n, int dim
 // draws moved from 0.75 to 16 units of 1.6e-3 A (the reference's own fp32 chain: 2.4), past that record's bar - not worth 12 us.
 constexpr int FWD_CHAIN_WAVES = 1, BWD_CHAIN_WAVES = 4;
 
+namespace {
+// the backbone scan, into the 14-slot layout (BB = false) or the compact backbone array (BB = true)
+template <bool BB>
+int launch_backbone_fwd(const float *ang, const int64_t *seq, int B, int L, float *crd, int32_t *status, void *stream) {
+  constexpr int nt = PT_WAVE * FWD_CHAIN_WAVES;
+  const size_t lds = (size_t)((3 * L + nt - 1) / nt) * nt * sizeof(float4);  // trig cache of the scan
+  auto kern = nerf_backbone_fwd_kernel<FWD_CHAIN_WAVES, BB>;
+  if (lds > 48 * 1024) {
+    PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  hipLaunchKernelGGL(kern, dim3(B), dim3(nt), lds, (hipStream_t)stream, ang, seq, L, crd, status);
+  return pt_check_launch();
+}
+}  // namespace
+
 extern "C" {
 
 int ptamd_sidechain_atoms(int residue) { return (residue < 0 || residue > 19) ? -1 : h_pt_nsc[residue]; }
@@ -694,18 +730,25 @@ size_t ptamd_nerf_workspace_bytes(int B, int L) { return (size_t)(B > 0 ? B : 0)
 int ptamd_nerf_fwd(const float *ang, const int64_t *seq, int B, int L, float *crd, int32_t *status, void *stream) {
   if (B <= 0 || L <= 0) return PTAMD_ERR_BAD_SHAPE;
   if (L > MAX_L_CHAIN) return PTAMD_ERR_TOO_LONG;
-  constexpr int nt = PT_WAVE * FWD_CHAIN_WAVES;
-  const size_t lds = (size_t)((3 * L + nt - 1) / nt) * nt * sizeof(float4);  // trig cache of the scan
-  if (lds > 48 * 1024) {
-    PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(nerf_backbone_fwd_kernel<FWD_CHAIN_WAVES>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  hipLaunchKernelGGL(nerf_backbone_fwd_kernel<FWD_CHAIN_WAVES>, dim3(B), dim3(nt), lds, (hipStream_t)stream, ang, seq, L, crd,
-                     status);
-  int rc = pt_check_launch();
+  int rc = launch_backbone_fwd<false>(ang, seq, B, L, crd, status, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(nerf_sidechain_fwd_kernel, dim3((L + SC_BLOCK - 1) / SC_BLOCK, B), dim3(SC_BLOCK), 0,
                      (hipStream_t)stream, ang, seq, L, crd);
+  return pt_check_launch();
+}
+
+int ptamd_nerf_bb_fwd(const float *ang, const int64_t *seq, int B, int L, float *crd_bb, int32_t *status, void *stream) {
+  if (B <= 0 || L <= 0) return PTAMD_ERR_BAD_SHAPE;
+  if (L > MAX_L_CHAIN) return PTAMD_ERR_TOO_LONG;
+  return launch_backbone_fwd<true>(ang, seq, B, L, crd_bb, status, stream);
+}
+
+int ptamd_nerf_bb_bwd(const float *ang, const int64_t *seq, const float *crd_bb, const float *dcrd_bb, int B, int L,
+                      float *dang, void *stream) {
+  if (B <= 0 || L <= 0) return PTAMD_ERR_BAD_SHAPE;
+  if (L > MAX_L_CHAIN) return PTAMD_ERR_TOO_LONG;
+  auto kern = nerf_backbone_bwd_kernel<BWD_CHAIN_WAVES, true>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(PT_WAVE * BWD_CHAIN_WAVES), 0, (hipStream_t)stream, ang, seq, crd_bb, dcrd_bb, L, dang);
   return pt_check_launch();
 }
 
@@ -719,8 +762,8 @@ int ptamd_nerf_bwd(const float *ang, const int64_t *seq, const float *crd, const
                      (hipStream_t)stream, ang, seq, crd, dcrd, L, dang, gbb);
   int rc = pt_check_launch();
   if (rc) return rc;
-  hipLaunchKernelGGL(nerf_backbone_bwd_kernel<BWD_CHAIN_WAVES>, dim3(B), dim3(PT_WAVE * BWD_CHAIN_WAVES), 0, (hipStream_t)stream,
-                     ang, seq, crd, gbb, L, dang);
+  auto kern = nerf_backbone_bwd_kernel<BWD_CHAIN_WAVES, false>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(PT_WAVE * BWD_CHAIN_WAVES), 0, (hipStream_t)stream, ang, seq, crd, gbb, L, dang);
   return pt_check_launch();
 }
 

@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from .protein.Sequence import VOCAB
 from .protein.structure_utils import get_backbone_from_full_coords  # noqa: F401  (losses.py:12: importable from here too)
-from .protein.Structure import (NUM_PREDICTED_ANGLES, NUM_PREDICTED_COORDS, SC_ANGLES_START_POS, generate_coords,
+from .protein.Structure import (NUM_BB_ATOMS, NUM_PREDICTED_ANGLES, NUM_PREDICTED_COORDS, SC_ANGLES_START_POS, generate_coords,
                                 nerf_backward, nerf_forward, raise_for_status)
 
 
@@ -60,15 +60,26 @@ def inverse_trig_transform(t):
 
 
 # ----------------------------------------------------------------------------- dRMSD
-def drmsd_forward_backward(pred_crd, true_crd, seq, need_grad=True, partial_budget_bytes=0):
+def drmsd_forward_backward(pred_crd, true_crd, seq, need_grad=True, partial_budget_bytes=0, backbone_only=False):
     """Batched loss kernel. Returns stats [B,8] (device) and d(drmsd/n)/d(pred_crd) or None.  `partial_budget_bytes`: cap on the
-    fixed-order partial sums of the pair sweep (0 = the library's 200 MB; smaller = the sweep runs in passes, same bits)."""
+    fixed-order partial sums of the pair sweep (0 = the library's 200 MB; smaller = the sweep runs in passes, same bits).
+    `backbone_only`: the dRMSD over the present N, CA, C alone (losses.py:83-92) - pred_crd is the compact [B,L*3,3] array of
+    nerf_forward(..., backbone_only=True), true_crd stays [B,L*14,3]; stats[:, 2], [:, 3], [:, 5] are what the full call reports
+    there and [:, 0], [:, 1], [:, 4] mirror them; the gradient is d(bb_drmsd/n_bb)/d(pred_crd), [B,L*3,3]."""
     _lib.require_gpu(pred_crd, true_crd, seq)
     B, L = seq.shape
     pred_crd, true_crd, seq = pred_crd.contiguous(), true_crd.contiguous(), seq.contiguous()
     stats = torch.empty(B, 8, dtype=torch.float32, device=seq.device)
     dcrd = torch.empty_like(pred_crd) if need_grad else None
     budget = int(partial_budget_bytes)
+    if backbone_only:
+        assert pred_crd.shape == (B, L * NUM_BB_ATOMS, 3) and true_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3)
+        nbytes = _lib.lib().ptamd_drmsd_bb_workspace_bytes_budget(B, L, budget)
+        ws = _lib.workspace("drmsd_bb", nbytes, seq.device)
+        rc = _lib.lib().ptamd_drmsd_bb_fwd_bwd_budget(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, _lib.ptr(stats),
+                                                      _lib.ptr(dcrd), _lib.ptr(ws), ws.numel(), budget, _lib.stream())
+        _lib.check(rc, "drmsd_bb_fwd_bwd")
+        return stats, dcrd
     nbytes = _lib.lib().ptamd_drmsd_workspace_bytes_budget(B, L, budget)
     ws = _lib.workspace("drmsd", nbytes, seq.device)
     rc = _lib.lib().ptamd_drmsd_fwd_bwd_budget(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, _lib.ptr(stats),
@@ -135,21 +146,26 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
     return generate_coords(angles, seq)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False):
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False):
     """Device-resident core of compute_batch_drmsd: no host synchronisation.
 
     Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
     `return_crd`, the predicted coordinates [B, L*14, 3] as a fourth value.
+
+    `backbone_only` (losses.py:83-92, --backbone_loss): the loss over N, CA, C alone - the backbone chain kernels without the
+    side-chain builder, the pair sweep over 3 L atoms per protein.  stats[:, 2], [:, 3], [:, 5] (mirrored in [:, 0], [:, 1],
+    [:, 4]) are the backbone numbers of the full call, the gradient is d(sum_i lndrmsd-bb_i)/d(pred_sincos) - exactly zero in the
+    side-chain channels - and the coordinates of `return_crd` are the compact [B, L*3, 3] backbone.
     """
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
-    crd, status = nerf_forward(ang, input_seqs)
-    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward)
+    crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
+    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward, backbone_only=backbone_only)
     grad = None
     if do_backward:
-        dang = nerf_backward(ang, input_seqs, crd, dcrd)
+        dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
     return (stats, grad, status, crd) if return_crd else (stats, grad, status)
 
@@ -280,15 +296,21 @@ def compute_batch_drmsd(pred_angs, true_crds, input_seqs, device=None, return_rm
     d(lndrmsd_i)/d(pred_angs) is back-propagated through pred_angs (losses.py:166-167).
     Returns np.mean over proteins of (drmsd, lndrmsd, bb drmsd, bb lndrmsd[, rmsd]); under data parallelism the means
     are those of the global batch (every rank calls this with its shard).
+
+    `backbone_only` (what losses.py:83-92 means; the reference's own code throws there): loss and gradient are
+    those of the backbone atoms N, CA, C alone; the tuple keeps its shape and its first two entries carry the backbone values
+    too.  The RMSD of `return_rmsd` is still that of all atoms (one full build beside the backbone path).
     """
-    if backbone_only:
-        raise NotImplementedError("--backbone_loss is broken in the reference too (SURVEY.md A-4)")
     dev = pred_angs.device
     true_crds, input_seqs = true_crds.to(dev), input_seqs.to(dev)
-    stats, grad, status, crd = batch_loss(pred_angs, true_crds, input_seqs, do_backward, return_crd=True)
+    stats, grad, status, crd = batch_loss(pred_angs, true_crds, input_seqs, do_backward, return_crd=True,
+                                          backbone_only=backbone_only)
     rmsd = None
     if return_rmsd:
         from .eval_metrics import kabsch_rmsd_batch
+        if backbone_only:
+            crd, _ = nerf_forward(angles_forward(pred_angs.detach().float().contiguous().view(*input_seqs.shape, -1)), input_seqs,
+                                  status=status)
         rmsd = kabsch_rmsd_batch(crd, true_crds, input_seqs)
     # The copy to the host is enqueued right behind the loss kernels and the host waits for THAT copy only after the
     # whole backward pass has been enqueued: waiting on the stream instead would drain the queue at the end of every
@@ -305,21 +327,23 @@ def compute_batch_drmsd(pred_angs, true_crds, input_seqs, device=None, return_rm
 
 
 def drmsd_work(pred_ang, true_crd, input_seq, return_rmsd=False, do_backward=True, backbone_only=False):
-    """One protein (losses.py:49-98): returns (grad [L,12] or None, drmsd, lndrmsd, bb, bb_ln[, rmsd])."""
-    if backbone_only:
-        raise NotImplementedError("--backbone_loss is broken in the reference too (SURVEY.md A-4)")
+    """One protein (losses.py:49-98): returns (grad [L,12] or None, drmsd, lndrmsd, bb, bb_ln[, rmsd]).
+    `backbone_only`: gradient and all four numbers are those of the backbone atoms alone (the first pair repeats the second);
+    the RMSD is that of all atoms."""
     dev = torch.device("cuda", torch.cuda.current_device())
     ang = torch.as_tensor(np.asarray(pred_ang) if not torch.is_tensor(pred_ang) else pred_ang).to(dev, torch.float32)[None]
     crd_t = torch.as_tensor(np.asarray(true_crd) if not torch.is_tensor(true_crd) else true_crd).to(dev, torch.float32)[None]
     seq = torch.as_tensor(np.asarray(input_seq) if not torch.is_tensor(input_seq) else input_seq).to(dev, torch.int64)[None]
-    crd, status = nerf_forward(ang.contiguous(), seq)
-    stats, dcrd = drmsd_forward_backward(crd, crd_t, seq, need_grad=do_backward)
-    grad = nerf_backward(ang.contiguous(), seq, crd, dcrd)[0].cpu() if do_backward else None
+    crd, status = nerf_forward(ang.contiguous(), seq, backbone_only=backbone_only)
+    stats, dcrd = drmsd_forward_backward(crd, crd_t, seq, need_grad=do_backward, backbone_only=backbone_only)
+    grad = nerf_backward(ang.contiguous(), seq, crd, dcrd, backbone_only=backbone_only)[0].cpu() if do_backward else None
     raise_for_status(int(status.item()), theta_is_error=False)
     s = stats[0].cpu().numpy().astype(np.float64)
     out = (grad, float(s[0]), float(s[1]), float(s[2]), float(s[3]))
     if return_rmsd:
         from .eval_metrics import kabsch_rmsd_batch
+        if backbone_only:
+            crd, _ = nerf_forward(ang.contiguous(), seq)
         out = out + (float(kabsch_rmsd_batch(crd, crd_t, seq)[0]),)
     return out
 

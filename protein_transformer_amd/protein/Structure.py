@@ -11,6 +11,7 @@ from .Sequence import VOCAB
 
 NUM_PREDICTED_ANGLES = 12
 NUM_PREDICTED_COORDS = 14
+NUM_BB_ATOMS = 3          # N, CA, C: slots 0..2 of a residue's 14 (structure_utils.py:19-32)
 NUM_BB_TORSION_ANGLES = 3
 NUM_BB_OTHER_ANGLES = 3
 NUM_SC_ANGLES = NUM_PREDICTED_ANGLES - (NUM_BB_OTHER_ANGLES + NUM_BB_TORSION_ANGLES)
@@ -41,25 +42,35 @@ def _status_word(device):
     return blk[used:used + 1]
 
 
-def nerf_forward(ang, seq, status=None):
-    """ang [B,L,12] fp32 cuda (radians), seq [B,L] int64 cuda -> crd [B,L*14,3]; no sync."""
+def nerf_forward(ang, seq, status=None, backbone_only=False):
+    """ang [B,L,12] fp32 cuda (radians), seq [B,L] int64 cuda -> crd [B,L*14,3]; no sync.
+    `backbone_only`: N, CA, C alone, as the COMPACT array [B,L*3,3] (bit for bit slots 0..2 of the full build; no side chains)."""
     _lib.require_gpu(ang, seq)
     B, L, _ = ang.shape
     ang = ang.contiguous()
     seq = seq.contiguous()
-    crd = torch.empty(B, L * NUM_PREDICTED_COORDS, 3, dtype=torch.float32, device=ang.device)
+    per_res = NUM_BB_ATOMS if backbone_only else NUM_PREDICTED_COORDS
+    crd = torch.empty(B, L * per_res, 3, dtype=torch.float32, device=ang.device)
     if status is None:
         status = _status_word(ang.device)
-    rc = _lib.lib().ptamd_nerf_fwd(_lib.ptr(ang), _lib.ptr(seq), B, L, _lib.ptr(crd), _lib.ptr(status), _lib.stream())
-    _lib.check(rc, "nerf_fwd")
+    fn = _lib.lib().ptamd_nerf_bb_fwd if backbone_only else _lib.lib().ptamd_nerf_fwd
+    rc = fn(_lib.ptr(ang), _lib.ptr(seq), B, L, _lib.ptr(crd), _lib.ptr(status), _lib.stream())
+    _lib.check(rc, "nerf_bb_fwd" if backbone_only else "nerf_fwd")
     return crd, status
 
 
-def nerf_backward(ang, seq, crd, dcrd):
-    """Adjoint of nerf_forward: dcrd [B,L*14,3] -> dang [B,L,12]."""
+def nerf_backward(ang, seq, crd, dcrd, backbone_only=False):
+    """Adjoint of nerf_forward: dcrd [B,L*14,3] -> dang [B,L,12].  `backbone_only`: crd and dcrd are the compact [B,L*3,3]
+    arrays of nerf_forward(..., backbone_only=True); the channels that cannot move N, CA or C come back as exact zeros."""
     _lib.require_gpu(ang, seq, crd, dcrd)
     B, L, _ = ang.shape
     dang = torch.empty_like(ang)
+    if backbone_only:
+        assert crd.shape == (B, L * NUM_BB_ATOMS, 3) and dcrd.shape == crd.shape
+        rc = _lib.lib().ptamd_nerf_bb_bwd(_lib.ptr(ang.contiguous()), _lib.ptr(seq.contiguous()), _lib.ptr(crd.contiguous()),
+                                          _lib.ptr(dcrd.contiguous()), B, L, _lib.ptr(dang), _lib.stream())
+        _lib.check(rc, "nerf_bb_bwd")
+        return dang
     nbytes = _lib.lib().ptamd_nerf_workspace_bytes(B, L)
     ws = _lib.workspace("nerf", nbytes, ang.device)
     rc = _lib.lib().ptamd_nerf_bwd(_lib.ptr(ang.contiguous()), _lib.ptr(seq.contiguous()), _lib.ptr(crd.contiguous()),

@@ -105,19 +105,38 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     the GLOBAL batch and the MSE gradient is normalised by the global count of selected elements, so that the SUM of
     the ranks' parameter gradients is the single-process gradient.  `pred` may be None for an
     empty shard.
+
+    `args.backbone_loss` (what losses.py:83-92 means; the reference's own code throws there): the dRMSD term is
+    that of the backbone atoms N, CA, C.  `-l drmsd` reports `loss = drmsd-bb`, `-l lndrmsd` `loss = lndrmsd-bb`, `-l combined`
+    combines lndrmsd-bb with the full-angle MSE; the injected gradient is d(sum_i lndrmsd-bb_i) (+ the unchanged MSE term) and is
+    exactly zero in the side-chain channels; `-l mse` ignores the flag.  A TRAINING step under the flag builds no side chains
+    (backbone chain kernels and a pair sweep over 3 L atoms only), so no full-atom dRMSD exists in it: the dictionary keeps its
+    10 keys and `drmsd-full` / `lndrmsd-full` / `combined-full` carry the BACKBONE values there.  Evaluation (`eval_mode`) builds
+    the whole structure and reports every metric as without the flag (`rmsd-full` needs all atoms); only `loss` follows the rule.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
     need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined"] or eval_mode
-    if getattr(args, "backbone_loss", False) and need_drmsd:
-        raise NotImplementedError("--backbone_loss is broken in the reference too (SURVEY.md A-4)")
+    backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
     sums = stats = grad = status = rmsd = None
     if not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
-            stats, grad, status, crd = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True)
+            if backbone and not eval_mode:
+                stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
+                crd = None
+            else:
+                stats, grad, status, crd = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards and not backbone,
+                                                      return_crd=True)
+                if backbone and do_backwards:              # evaluation that also back-propagates: the gradient is the backbone's
+                    grad = batch_loss(pred, tgt_crds, src_seq, do_backward=True, backbone_only=True)[1]
             if return_rmsd:
                 from .eval_metrics import kabsch_rmsd_batch
+                if crd is None:                            # all atoms, for the RMSD alone
+                    from .losses import angles_forward
+                    from .protein.Structure import nerf_forward
+                    crd, _ = nerf_forward(angles_forward(pred.detach().float().contiguous().view(*src_seq.shape, -1)), src_seq,
+                                          status=status)
                 rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
     report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res)
     if do_backwards and not empty:
@@ -140,11 +159,13 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         d_loss, ln_d_loss, d_bb_loss, d_bb_ln_loss = (np.float64(host[k]) for k in ("drmsd", "lndrmsd", "drmsd-bb", "lndrmsd-bb"))
         c_loss = combine_drmsd_mse(ln_d_loss, m_loss_full, w=args.combined_drmsd_weight, log=log)
         if args.loss == "lndrmsd":
-            loss = ln_d_loss
+            loss = d_bb_ln_loss if backbone else ln_d_loss
         elif args.loss == "drmsd":
-            loss = d_loss
+            loss = d_bb_loss if backbone else d_loss
         elif args.loss == "combined":
-            loss = c_loss
+            # (a training step under the flag: ln_d_loss IS the backbone value; only evaluation has two different numbers)
+            loss = combine_drmsd_mse(d_bb_ln_loss, m_loss_full, w=args.combined_drmsd_weight, log=False) \
+                if backbone and eval_mode else c_loss
         else:
             loss = m_loss_full
     else:
