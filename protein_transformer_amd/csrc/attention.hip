@@ -18,30 +18,11 @@
 //     deterministic.
 //   * dropout masks come from a counter hash of (seed, protein*head, query, key) and are regenerated in the
 //     backward kernels instead of being stored.
+#include "attention_internal.h"
 #include "attn_dropout.h"
 #include "kv_format.h"
 
-// split-bf16 variants for dk = 64 and dk = 32 (attention_split.hip), selected by the `arith` argument of the entry points
-int pt_attention_fwd_split(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float p, uint64_t seed,
-                           uint32_t sid, float *out, float *lse, hipStream_t st);
-int pt_attention_bwd_split(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
-                           float *delta, int B, int L, int H, int dk, float p, uint64_t seed, uint32_t sid, float *dqkv,
-                           hipStream_t st);
-// two-term f16 variants (attention_f16x2.hip): arith = PTAMD_GEMM_AUTO / PTAMD_GEMM_F16X2
-int pt_attention_fwd_f16x2(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float p, uint64_t seed,
-                           uint32_t sid, float *out, float *lse, uint32_t *keep_bits, const void *kv_planes, const float *kv_inv,
-                           hipStream_t st);
-int pt_attention_bwd_f16x2(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
-                           float *delta, int B, int L, int H, int dk, float p, uint64_t seed, uint32_t sid, float *dqkv,
-                           uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits, const void *kv_planes,
-                           const float *kv_inv, float *slabs, size_t slab_floats, hipStream_t st);
-size_t pt_attention_bwd_f16x2_slab_floats(int B, int L, int H, int dk);
-bool pt_attention_bwd_f16x2_reads_keep_bits(int B, int L, int H, int dk);
-bool pt_attention_f16x2_reads_kv_planes(int B, int L, int H, int dk);
-
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int QB = 128;  // queries (or keys) per workgroup
 constexpr int KT = 64;   // keys per LDS tile in the forward / dQ kernels
@@ -51,10 +32,6 @@ constexpr int QT = 32;   // queries per LDS tile in the dK/dV kernel
 // SIMD) and row fragments of 64 floats, so it takes the whole register file
 template <int DK>
 constexpr int F32_WAVES = DK == 128 ? 1 : 2;
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-// row index inside a 32x32 MFMA C tile held by (register r, lane half lh)
-__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // ---- cooperative tile staging: rows x DK floats from a [*, ld] matrix into an LDS image with stride DK+1
 template <int DK, int ROWS>
@@ -474,36 +451,35 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dkv_kernel(const 
 }
 
 template <int DK>
-int launch_fwd(const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
-               float *out, float *lse, hipStream_t st) {
-  hipLaunchKernelGGL(attn_fwd_kernel<DK>, dim3((L + QB - 1) / QB, H, B), dim3(256), 0, st, qkv, seq, L, H, p, seed, sid,
-                     out, lse);
-  return pt_check_launch();
+int launch_fwd(const AttnArgs &a, const AttnFwd &f) {
+  return attn_launch(attn_fwd_kernel<DK>, dim3((a.L + QB - 1) / QB, a.H, a.B), dim3(256), 0, a.stream, a.qkv, a.seq, a.L, a.H,
+                     a.p, a.seed, a.sid, f.out, f.lse);
 }
 template <int DK>
-int launch_bwd(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse, float *delta,
-               int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *dqkv, hipStream_t st) {
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<DK>, grid, dim3(256), 0, st, qkv, seq, o_fwd, d_o, lse, delta, L, H, p, seed, sid,
-                     dqkv);
-  int rc = pt_check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<DK>, grid, dim3(256), 0, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv);
-  return pt_check_launch();
+int launch_bwd(const AttnArgs &a, const AttnBwd &b) {
+  const dim3 grid((a.L + QB - 1) / QB, a.H, a.B);
+  if (int rc = attn_launch(attn_bwd_dq_kernel<DK>, grid, dim3(256), 0, a.stream, a.qkv, a.seq, b.o_fwd, b.d_o, b.lse, b.delta,
+                           a.L, a.H, a.p, a.seed, a.sid, b.dqkv))
+    return rc;
+  return attn_launch(attn_bwd_dkv_kernel<DK>, grid, dim3(256), 0, a.stream, a.qkv, a.seq, b.d_o, b.lse, b.delta, a.L, a.H, a.p,
+                     a.seed, a.sid, b.dqkv);
+}
+
+// what both entry points refuse before they look at anything else
+bool bad_call(int B, int L, int H, int arith, float p) {
+  return B <= 0 || L <= 0 || H <= 0 || arith < PTAMD_GEMM_F32 || arith > PTAMD_GEMM_AUTO || p < 0.f || p >= 1.f;
 }
 
 }  // namespace
 
 extern "C" {
 
-namespace {
-size_t delta_floats(int B, int L, int H) { return ((size_t)B * H * L + 3) & ~(size_t)3; }   // (what follows stays 16-byte aligned)
-}
 size_t ptamd_attention_workspace_bytes(int B, int L, int H, int dk) {
   if (B <= 0 || L <= 0 || H <= 0) return 0;
   // delta [B, H, L]; behind it the slabs of the split one-sweep backward kernel where this shape takes it (head size 64, few
-  // (protein, head) pairs: csrc/attention_f16x2.hip fused_split)
-  return (delta_floats(B, L, H) + pt_attention_bwd_f16x2_slab_floats(B, L, H, dk)) * sizeof(float);
+  // (protein, head) pairs: csrc/attention_f16x2.hip launch_sweep)
+  const size_t slabs = attn_family(dk, PTAMD_GEMM_AUTO) == ATTN_F16X2 ? pt_attention_bwd_f16x2_slab_floats(B, L, H, dk) : 0;
+  return (attn_delta_floats(B, L, H) + slabs) * sizeof(float);
 }
 
 size_t ptamd_attention_keep_bits_bytes(int B, int L, int H) {
@@ -511,66 +487,50 @@ size_t ptamd_attention_keep_bits_bytes(int B, int L, int H) {
   return attn_keep_words(B, L, H) * sizeof(uint32_t);
 }
 
+// (the one-sweep kernel and, on the two-kernel path, the dK / dV kernel - both keep keys in lanes; the dQ kernel draws them)
 int ptamd_attention_bwd_reads_keep_bits(int B, int L, int H, int dk, int arith) {
-  if (B <= 0 || L <= 0 || H <= 0 || !(arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2)) return 0;
-  return pt_attention_bwd_f16x2_reads_keep_bits(B, L, H, dk) ? 1 : 0;
+  return B > 0 && L > 0 && H > 0 && attn_family(dk, arith) == ATTN_F16X2;
 }
 
 size_t ptamd_attention_kv_bytes(int T, int H) { return (T <= 0 || H <= 0) ? 0 : ptkv::planes_bytes(T, H); }
 size_t ptamd_attention_kv_inv_floats(int T, int H) { return (T <= 0 || H <= 0) ? 0 : ptkv::inv_floats(T, H); }
 int ptamd_attention_reads_kv_planes(int B, int L, int H, int dk, int arith) {
-  if (B <= 0 || L <= 0 || H <= 0 || !(arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2)) return 0;
-  return pt_attention_f16x2_reads_kv_planes(B, L, H, dk) ? 1 : 0;
+  return B > 0 && L > 0 && H > 0 && attn_family(dk, arith) == ATTN_F16X2 && pt_attention_f16x2_reads_kv_planes(B, L, H, dk);
 }
 
 int ptamd_attention_fwd(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float dropout_p,
                         uint64_t seed, uint32_t stream_id, int arith, float *out, float *lse, uint32_t *keep_bits,
                         const void *kv_planes, const float *kv_inv, void *stream) {
-  if (B <= 0 || L <= 0 || H <= 0 || arith < PTAMD_GEMM_F32 || arith > PTAMD_GEMM_AUTO) return PTAMD_ERR_BAD_SHAPE;
-  if (dropout_p < 0.f || dropout_p >= 1.f) return PTAMD_ERR_BAD_SHAPE;
+  if (bad_call(B, L, H, arith, dropout_p)) return PTAMD_ERR_BAD_SHAPE;
   if (!pt_aligned16(qkv) || !pt_aligned16(out)) return PTAMD_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  const bool f16x2 = (dk == 64 || dk == 32 || dk == 128) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2);
-  if (keep_bits && !f16x2) return PTAMD_ERR_BAD_SHAPE;  // the decisions are a by-product of the f16x2 kernels only
-  if (kv_planes && !(f16x2 && kv_inv && pt_aligned16(kv_planes))) return PTAMD_ERR_BAD_SHAPE;   // ... the planes their input only
-  if (f16x2) return pt_attention_fwd_f16x2(qkv, seq, B, L, H, dk, dropout_p, seed, stream_id, out, lse, keep_bits, kv_planes, kv_inv, st);
-  if ((dk == 64 || dk == 32) && arith != PTAMD_GEMM_F32)
-    return pt_attention_fwd_split(qkv, seq, B, L, H, dk, dropout_p, seed, stream_id, out, lse, st);
-  switch (dk) {
-    case 8: return launch_fwd<8>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
-    case 16: return launch_fwd<16>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
-    case 32: return launch_fwd<32>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
-    case 64: return launch_fwd<64>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
-    case 128: return launch_fwd<128>(qkv, seq, B, L, H, dropout_p, seed, stream_id, out, lse, st);
-    default: return PTAMD_ERR_BAD_SHAPE;
-  }
+  const AttnFamily fam = attn_family(dk, arith);
+  if (keep_bits && fam != ATTN_F16X2) return PTAMD_ERR_BAD_SHAPE;  // the decisions are a by-product of the f16x2 kernels only
+  if (kv_planes && !(fam == ATTN_F16X2 && kv_inv && pt_aligned16(kv_planes))) return PTAMD_ERR_BAD_SHAPE;   // ... the planes their input only
+  const AttnArgs a = {qkv, seq, B, L, H, dk, dropout_p, seed, stream_id, (hipStream_t)stream};
+  const AttnFwd f = {out, lse, keep_bits};
+  if (fam == ATTN_F16X2) return pt_attention_fwd_f16x2(a, f, AttnKv{static_cast<const char *>(kv_planes), kv_inv});
+  if (fam == ATTN_BF16X3) return pt_attention_fwd_split(a, f);
+  return attn_by_dk<8, 16, 32, 64, 128>(dk, [&](auto DK) { return launch_fwd<decltype(DK)::value>(a, f); });
 }
 
 int ptamd_attention_bwd(const float *qkv, const int64_t *seq, const float *out, const float *dout, const float *lse,
                         int B, int L, int H, int dk, float dropout_p, uint64_t seed, uint32_t stream_id, int arith,
                         float *dqkv, uint32_t *row_scale, uint32_t *row_scale_min, const uint32_t *keep_bits,
                         const void *kv_planes, const float *kv_inv, void *workspace, size_t workspace_bytes, void *stream) {
-  if (B <= 0 || L <= 0 || H <= 0 || arith < PTAMD_GEMM_F32 || arith > PTAMD_GEMM_AUTO) return PTAMD_ERR_BAD_SHAPE;
-  if (dropout_p < 0.f || dropout_p >= 1.f) return PTAMD_ERR_BAD_SHAPE;
+  if (bad_call(B, L, H, arith, dropout_p)) return PTAMD_ERR_BAD_SHAPE;
   if (!workspace || workspace_bytes < ptamd_attention_workspace_bytes(B, L, H, dk)) return PTAMD_ERR_WORKSPACE;
   if (!pt_aligned16(qkv) || !pt_aligned16(out) || !pt_aligned16(dout) || !pt_aligned16(dqkv)) return PTAMD_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
+  const AttnFamily fam = attn_family(dk, arith);
+  // by-products / inputs of the f16x2 kernels only
+  if (fam != ATTN_F16X2 && (row_scale || row_scale_min || keep_bits || kv_planes)) return PTAMD_ERR_BAD_SHAPE;
   float *delta = static_cast<float *>(workspace);
-  if ((dk == 64 || dk == 32 || dk == 128) && (arith == PTAMD_GEMM_AUTO || arith == PTAMD_GEMM_F16X2))
-    return pt_attention_bwd_f16x2(qkv, seq, out, dout, lse, delta, B, L, H, dk, dropout_p, seed, stream_id, dqkv, row_scale,
-                                  row_scale ? row_scale_min : nullptr, keep_bits, kv_planes, kv_inv, delta + delta_floats(B, L, H),
-                                  workspace_bytes / sizeof(float) - delta_floats(B, L, H), st);
-  if (row_scale || row_scale_min || keep_bits || kv_planes) return PTAMD_ERR_BAD_SHAPE;  // by-products / inputs of the f16x2 kernels only
-  if ((dk == 64 || dk == 32) && arith != PTAMD_GEMM_F32)
-    return pt_attention_bwd_split(qkv, seq, out, dout, lse, delta, B, L, H, dk, dropout_p, seed, stream_id, dqkv, st);
-  switch (dk) {
-    case 8: return launch_bwd<8>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
-    case 16: return launch_bwd<16>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
-    case 32: return launch_bwd<32>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
-    case 64: return launch_bwd<64>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
-    case 128: return launch_bwd<128>(qkv, seq, out, dout, lse, delta, B, L, H, dropout_p, seed, stream_id, dqkv, st);
-    default: return PTAMD_ERR_BAD_SHAPE;
-  }
+  const size_t nd = attn_delta_floats(B, L, H);
+  const AttnArgs a = {qkv, seq, B, L, H, dk, dropout_p, seed, stream_id, (hipStream_t)stream};
+  const AttnBwd b = {out, dout, lse, delta, dqkv, row_scale, row_scale ? row_scale_min : nullptr, keep_bits,
+                     delta + nd, workspace_bytes / sizeof(float) - nd};
+  if (fam == ATTN_F16X2) return pt_attention_bwd_f16x2(a, b, AttnKv{static_cast<const char *>(kv_planes), kv_inv});
+  if (fam == ATTN_BF16X3) return pt_attention_bwd_split(a, b);
+  return attn_by_dk<8, 16, 32, 64, 128>(dk, [&](auto DK) { return launch_bwd<decltype(DK)::value>(a, b); });
 }
 
 }  // extern "C"

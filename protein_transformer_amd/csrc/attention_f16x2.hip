@@ -1,4 +1,4 @@
-// Fused masked multi-head self-attention on the f16 matrix pipe with two-term operand splitting (dk = 64 and 32).
+// Fused masked multi-head self-attention on the f16 matrix pipe with two-term operand splitting (dk = 128, 64 and 32).
 //
 // Same operator, interface, masking, dropout hash and outputs as attention.hip / attention_split.hip
 //   /root/reference/protein_transformer/models/transformer/Attention.py:14-22,55-68
@@ -32,9 +32,9 @@
 // with the whole register file (their operands alone are 256 registers per lane).
 #include <stdlib.h>
 
+#include "attention_internal.h"
 #include "attn_dropout.h"
 #include "kv_format.h"
-#include "split_bf16.h"
 
 namespace ptattn16 {
 using namespace ptsplit;
@@ -51,7 +51,6 @@ constexpr int TR = 32;           // rows (keys or queries) of an LDS tile
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float TWO14 = 16384.f, INV_TWO14 = 1.f / 16384.f;
 
-__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 __device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 // 1 / x for x = 0 (-> 2^127, finite) or a power of two in [2^-126, 2^127]
 __device__ __forceinline__ float inv_pow2(float x) { return __uint_as_float((254u << 23) - __float_as_uint(x)); }
@@ -1794,33 +1793,17 @@ __global__ __launch_bounds__(256) void attn_bwd_split_reduce_kernel(const float 
   }
 }
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {  // idempotent, host-only: no state kept between calls
-  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return PTAMD_OK;
-}
-}  // namespace ptattn16
-
-namespace ptgemm {
-int persistent_grid(int reserved_cus);  // CUs of the current device (gemm.hip: a table filled once, no per-launch query)
-}
-namespace ptattn16 {
 namespace {
 // workgroup shape by the number of workgroups: 8 wavefronts (256 queries / keys); when those would cover at most half of
 // the CUs, 8 wavefronts as 4 groups x 2 halves of the streamed dimension (128 per workgroup; W4 = 4 plain wavefronts for
 // the dK/dV kernel, below); when even 128 per workgroup would, 4 wavefronts as 2 groups x 2 halves (64 per workgroup)
 enum Shape { W8 = 0, W4 = 1, W4_HALVES = 2, W8_HALVES = 3 };
-// In between (as many 128-query workgroups as CUs, or up to twice as many CUs): 8 wavefronts as 4 query groups x 2 halves
-// for the forward and dQ kernels - the same number of workgroups as with 4 wavefronts, half the tile loop, two
-// wavefronts per SIMD; the dK/dV kernel keeps 4 wavefronts there (it has no registers left for a second staged tile
-// pair at 8: 256 VGPRs already; built with 11 spilled registers it measured 0.5 % of a step).
-inline Shape dkv_shape(Shape sh) { return sh == W8_HALVES ? W4 : sh; }
 
 // The backward pass of head size 64 is one sweep over the keys that produces dQ, dK and dV together: UNSPLIT (one
 // workgroup per (protein, head)) where those pairs fill more than half of the chip; otherwise SPLIT (round 6) - the per-GPU
 // share of a strongly scaled batch (4 / 8 / 16 proteins x 512: 92 / ~135 / ~205 us of dQ + dK/dV kernels per layer) - a
 // workgroup per (pair, 256-key block), with the query tiles cut into `qs` ranges too where that is needed for about one
-// workgroup per CU.  Head size 32 takes the two-kernel path (dQ kernel, dK/dV kernel).
+// workgroup per CU.  Head sizes 32 and 128 take the two-kernel path (dQ kernel, dK/dV kernel).
 // PTAMD_ATTN_FUSED in the environment (read at every call; for tests, which run small batches, and for A/B measurements):
 // 0 = the two-kernel path, 1 = the unsplit sweep, 2 = the split sweep, whatever the batch (head size 64).  The choice changes
 // the summation order of dQ (two-kernel path) / of dK and dV (split ranges), nothing else.
@@ -1828,29 +1811,26 @@ enum Bwd { BWD_TWO_KERNELS, BWD_SWEEP, BWD_SPLIT };
 // Every kernel choice of one (B, L, H, dk): the forward pass, the backward pass and the workspace and K / V plane queries
 // all read it, so they cannot disagree.
 struct Plan {
-  Shape shape;      // forward and dQ kernels: W8, W8_HALVES or W4_HALVES (dkv_shape: the dK/dV kernel); head size 128:
-                    // W8 or W4 for the forward kernel, the backward kernels always W4
+  Shape fwd;        // W8, W8_HALVES or W4_HALVES; head size 128: W8 or W4 (no room for two halves of the keys)
   bool quarters;    // forward: 2 query groups x 4 key quarters in place of W4_HALVES
   Bwd bwd;
+  // the two-kernel path.  dQ: as the forward kernel.  dK/dV: W4 in place of W8_HALVES - the same number of workgroups, but
+  // it has no registers left for a second staged tile pair at 8 wavefronts (256 VGPRs already; built with 11 spilled
+  // registers it measured 0.5 % of a step).  Head size 128: W4 for both, whatever the forward shape.
+  Shape dq, dkv;
   int nkb, qs;      // split sweep: 256-key blocks, query ranges
   bool kv_planes;   // the forward and backward kernels read pre-split K / V (kv_format.h)
 };
 inline Plan plan(int B, int L, int H, int dk) {
   const size_t cus = (size_t)ptgemm::persistent_grid(0), bh = (size_t)H * B;
   Plan pl;
-  if (dk == 128) {  // W8 or W4 forward (no room for two halves of the keys), the two-kernel backward at 4 wavefronts
-    pl.shape = (size_t)((L + 255) / 256) * bh * 2 > cus ? W8 : W4;
-    pl.quarters = false;
-    pl.bwd = BWD_TWO_KERNELS;
-    pl.nkb = (L + FK - 1) / FK;
-    pl.qs = 1;
-    pl.kv_planes = false;
-    return pl;
-  }
-  if ((size_t)((L + 255) / 256) * bh * 2 > cus) pl.shape = W8;
-  else pl.shape = (size_t)((L + 127) / 128) * bh * 2 > cus ? W8_HALVES : W4_HALVES;
+  if ((size_t)((L + 255) / 256) * bh * 2 > cus) pl.fwd = W8;
+  else if (dk == 128) pl.fwd = W4;
+  else pl.fwd = (size_t)((L + 127) / 128) * bh * 2 > cus ? W8_HALVES : W4_HALVES;
+  pl.dq = dk == 128 ? W4 : pl.fwd;
+  pl.dkv = dk == 128 || pl.fwd == W8_HALVES ? W4 : pl.fwd;
   // the 2 x 4 forward shape where the key range has a tile for every quarter
-  pl.quarters = dk == 64 && pl.shape == W4_HALVES && L > 3 * TR;
+  pl.quarters = dk == 64 && pl.fwd == W4_HALVES && L > 3 * TR;
   pl.bwd = BWD_TWO_KERNELS;
   if (dk == 64) {
     if (const char *e = getenv("PTAMD_ATTN_FUSED")) pl.bwd = e[0] == '1' ? BWD_SWEEP : e[0] == '2' ? BWD_SPLIT : BWD_TWO_KERNELS;
@@ -1868,7 +1848,7 @@ inline Plan plan(int B, int L, int H, int dk) {
   }
   // pre-split K / V are read by the 256-query forward kernel and by the sweep with one workgroup per key block (unsplit, or
   // split with no query ranges - 16 proteins x 8 heads x 512): head size 64, whole 32-token tiles per protein
-  pl.kv_planes = B > 0 && L > 0 && H > 0 && dk == 64 && (L & 31) == 0 && pl.shape == W8 &&
+  pl.kv_planes = B > 0 && L > 0 && H > 0 && dk == 64 && (L & 31) == 0 && pl.fwd == W8 &&
                  (pl.bwd == BWD_SWEEP || (pl.bwd == BWD_SPLIT && pl.qs == 1));
   return pl;
 }
@@ -1879,155 +1859,93 @@ inline size_t split_floats(int B, int L, int H, const Plan &pl) {
   return (size_t)pl.nkb * T * D + (pl.qs > 1 ? (size_t)pl.qs * T * 2 * D : 0);
 }
 
-template <int DK, int NW, int PARTS>
-int launch_fwd(const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *out,
-               float *lse, uint32_t *keep_bits, hipStream_t st) {
-  constexpr int QB = 32 * NW / PARTS;
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
-  if (int rc = set_lds(attn_fwd_f16x2_kernel<DK, NW, PARTS>, LDS)) return rc;
-  hipLaunchKernelGGL((attn_fwd_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), LDS, st, qkv, seq, L, H, p, seed, sid, out, lse,
-                     keep_bits);
-  return pt_check_launch();
+// ---- a Shape as the <NW, PARTS> of attn_fwd_ / attn_bwd_dq_ / attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS>: written here, once.
+// The instantiations a pass has (the shapes plan() gives it): with two halves only below head size 128; plain 4 wavefronts
+// only for the dK/dV kernel and head size 128; 8 wavefronts on two halves not for the dK/dV kernel.
+enum Pass { FWD, DQ, DKV };
+constexpr bool built(Pass pass, int dk, int nw, int parts) {
+  if (dk == 128) return parts == 1 && (nw == 4 || pass == FWD);
+  return pass == DKV ? !(nw == 8 && parts == 2) : !(nw == 4 && parts == 1);
 }
-// 8 wavefronts as 2 query groups x 4 key quarters on unpadded tiles (round 6; head size 64): as many workgroups as 4 x (2 x 2)
-// - 64 queries each - with HALF the tile loop per wavefront and TWO wavefronts per SIMD (one wavefront per SIMD runs a tile in
-// 3.3 us, two in 1.5 each: the forward pass of the 4-protein share)
-int launch_fwd_quarters(const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *out,
-                        float *lse, uint32_t *keep_bits, hipStream_t st) {
-  constexpr size_t LDS = (size_t)4 * 2 * (2 * Tile2U::ELEMS) * sizeof(unsigned short);
-  auto kern = attn_fwd_f16x2_kernel<64, 8, 4, Tile2U>;
-  if (int rc = set_lds(kern, LDS)) return rc;
-  hipLaunchKernelGGL(kern, dim3((L + 63) / 64, H, B), dim3(512), LDS, st, qkv, seq, L, H, p, seed, sid, out, lse, keep_bits);
-  return pt_check_launch();
-}
-template <int DK, int NW, int PARTS>
-int launch_dq(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse, float *delta,
-              int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *dqkv, uint32_t *row_scale, uint32_t *row_min,
-              hipStream_t st) {
-  constexpr int QB = 32 * NW / PARTS;
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
-  if (int rc = set_lds(attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>, LDS)) return rc;
-  hipLaunchKernelGGL((attn_bwd_dq_f16x2_kernel<DK, NW, PARTS>), grid, dim3(64 * NW), LDS, st, qkv, seq, o_fwd, d_o, lse,
-                     delta, L, H, p, seed, sid, dqkv, row_scale, row_min);
-  return pt_check_launch();
-}
-template <int DK, int NW, int PARTS>
-int launch_dkv(const float *qkv, const int64_t *seq, const float *d_o, const float *lse, const float *delta, int B, int L, int H,
-               float p, uint64_t seed, uint32_t sid, float *dqkv, uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits,
-               hipStream_t st) {
-  constexpr int QB = 32 * NW / PARTS;
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  constexpr size_t LDS = PARTS * HALVES<DK> * ATTN_LDS;
-  if (keep_bits && p > 0.f) {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>, LDS)) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, true>), grid, dim3(64 * NW), LDS, st, qkv, seq, d_o, lse,
-                       delta, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits);
-  } else {
-    if (int rc = set_lds(attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>, LDS)) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_f16x2_kernel<DK, NW, PARTS, false>), grid, dim3(64 * NW), LDS, st, qkv, seq, d_o, lse,
-                       delta, L, H, p, seed, sid, dqkv, row_scale, row_min, nullptr);
+// launches a kernel of a <DK, NW, PARTS> family over the (32 NW / PARTS)-row blocks of every (protein, head)
+template <int DK, int NW_, int PARTS_>
+struct Tiled {
+  static constexpr int NW = NW_, PARTS = PARTS_;
+  const AttnArgs &a;
+  template <typename K, typename... A>
+  int operator()(K kernel, A... args) const {
+    constexpr int QB = 32 * NW / PARTS;
+    return attn_launch(kernel, dim3((a.L + QB - 1) / QB, a.H, a.B), dim3(64 * NW), PARTS * HALVES<DK> * ATTN_LDS, a.stream, args...);
   }
-  return pt_check_launch();
+};
+template <Pass PASS, int DK, int NW, int PARTS, typename F>
+int if_built(const AttnArgs &a, F &f) {
+  if constexpr (built(PASS, DK, NW, PARTS)) return f(Tiled<DK, NW, PARTS>{a});
+  else return PTAMD_ERR_BAD_SHAPE;
 }
-int launch_fwd_kvp(const float *qkv, const char *kvp, const float *kv_inv, const int64_t *seq, int B, int L, int H, float p,
-                   uint64_t seed, uint32_t sid, float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
-  if (int rc = set_lds(attn_fwd_kvp_f16x2_kernel, KvpGeo::LDS)) return rc;
-  hipLaunchKernelGGL(attn_fwd_kvp_f16x2_kernel, dim3((L + 255) / 256, H, B), dim3(512), KvpGeo::LDS, st, qkv, kvp, kv_inv,
-                     (B * L) / 32, seq, L, H, p, seed, sid, out, lse, keep_bits);
-  return pt_check_launch();
-}
-template <int DK>
-int fwd_by_plan(const Plan &pl, const float *qkv, const int64_t *seq, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
-                float *out, float *lse, uint32_t *keep_bits, hipStream_t st) {
-  if (pl.shape == W8) return launch_fwd<DK, 8, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  if constexpr (DK == 128) {  // W4
-    return launch_fwd<DK, 4, 1>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  } else {
-    if (pl.shape == W8_HALVES) return launch_fwd<DK, 8, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-    if (pl.quarters) return launch_fwd_quarters(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-    return launch_fwd<DK, 4, 2>(qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
+// f(Tiled<DK, NW, PARTS>) for the <NW, PARTS> of `sh`; a shape the pass has no kernel for is refused
+template <Pass PASS, int DK, typename F>
+int by_shape(Shape sh, const AttnArgs &a, F f) {
+  switch (sh) {
+    case W8: return if_built<PASS, DK, 8, 1>(a, f);
+    case W4: return if_built<PASS, DK, 4, 1>(a, f);
+    case W4_HALVES: return if_built<PASS, DK, 4, 2>(a, f);
+    default: return if_built<PASS, DK, 8, 2>(a, f);
   }
 }
-int launch_fused_split(const Plan &pl, const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o,
-                       const float *lse, float *delta, float *slabs, int B, int L, int H, float p, uint64_t seed, uint32_t sid,
-                       float *dqkv, uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits, const char *kvp,
-                       const float *kv_inv, hipStream_t st) {
-  const size_t items = (size_t)B * L * H * 16, T = (size_t)B * L;
-  const int D = H * 64;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, o_fwd, d_o, B * L, L, H, 64, delta);
-  const bool bits = keep_bits != nullptr && p > 0.f, ranges = pl.qs > 1;
-  float *dq_part = slabs, *dkv_part = slabs + (size_t)pl.nkb * T * D;
-  // (pre-split K / V only where the 256-query forward kernel reads them too: one workgroup per key block, no query ranges)
-  auto kern = ranges ? (bits ? attn_bwd_fused_f16x2_kernel<true, false, 2> : attn_bwd_fused_f16x2_kernel<false, false, 2>)
-              : kvp  ? (bits ? attn_bwd_fused_f16x2_kernel<true, true, 1> : attn_bwd_fused_f16x2_kernel<false, true, 1>)
-                     : (bits ? attn_bwd_fused_f16x2_kernel<true, false, 1> : attn_bwd_fused_f16x2_kernel<false, false, 1>);
-  if (kvp && ranges) return PTAMD_ERR_BAD_SHAPE;
-  if (int rc = set_lds(kern, FUSED_LDS)) return rc;
-  hipLaunchKernelGGL(kern, dim3(pl.nkb * pl.qs, H, B), dim3(512), FUSED_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv,
-                     row_scale, row_min, keep_bits, kvp, kv_inv, (B * L) / 32, dq_part, dkv_part, pl.qs);
-  int rc = pt_check_launch();
-  if (rc) return rc;
-  const dim3 rgrid((unsigned)((T + 7) / 8));
-  if (ranges)
-    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<true>, rgrid, dim3(256), 0, st, dq_part, pl.nkb, dkv_part, pl.qs, T, D, dqkv,
-                       row_scale, row_min);
-  else
-    hipLaunchKernelGGL(attn_bwd_split_reduce_kernel<false>, rgrid, dim3(256), 0, st, dq_part, pl.nkb, dkv_part, pl.qs, T, D, dqkv,
-                       row_scale, row_min);
-  return pt_check_launch();
-}
-int launch_fused(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse, float *delta,
-                 int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *dqkv, uint32_t *row_scale,
-                 uint32_t *row_min, const uint32_t *keep_bits, const char *kvp, const float *kv_inv, hipStream_t st) {
-  const size_t items = (size_t)B * L * H * 16;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, o_fwd, d_o, B * L, L, H, 64, delta);
-  const bool bits = keep_bits != nullptr && p > 0.f;
-  auto kern = kvp ? (bits ? attn_bwd_fused_f16x2_kernel<true, true> : attn_bwd_fused_f16x2_kernel<false, true>)
-                  : (bits ? attn_bwd_fused_f16x2_kernel<true, false> : attn_bwd_fused_f16x2_kernel<false, false>);
-  if (int rc = set_lds(kern, FUSED_LDS)) return rc;
-  hipLaunchKernelGGL(kern, dim3(1, H, B), dim3(512), FUSED_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed, sid, dqkv, row_scale,
-                     row_min, keep_bits, kvp, kv_inv, (B * L) / 32, (float *)nullptr, (float *)nullptr, 1);
-  return pt_check_launch();
-}
+
 template <int DK>
-int bwd_by_shape(Shape sh, const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
-                 float *delta, int B, int L, int H, float p, uint64_t seed, uint32_t sid, float *dqkv, uint32_t *row_scale,
-                 uint32_t *row_min, const uint32_t *keep_bits, hipStream_t st) {
-  int rc;
-  if (sh == W8) rc = launch_dq<DK, 8, 1>(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, st);
-  else if (sh == W8_HALVES) rc = launch_dq<DK, 8, 2>(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, st);
-  else rc = launch_dq<DK, 4, 2>(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, st);
+int launch_fwd(const Plan &pl, const AttnArgs &a, const AttnFwd &f) {
+  return by_shape<FWD, DK>(pl.fwd, a, [&](auto t) {
+    return t(attn_fwd_f16x2_kernel<DK, t.NW, t.PARTS>, a.qkv, a.seq, a.L, a.H, a.p, a.seed, a.sid, f.out, f.lse, f.keep_bits);
+  });
+}
+// (the forward kernel's decisions are read by the dK / dV kernel; BITS: see there)
+template <int DK>
+int launch_two_kernels(const Plan &pl, const AttnArgs &a, const AttnBwd &b) {
+  const int rc = by_shape<DQ, DK>(pl.dq, a, [&](auto t) {
+    return t(attn_bwd_dq_f16x2_kernel<DK, t.NW, t.PARTS>, a.qkv, a.seq, b.o_fwd, b.d_o, b.lse, b.delta, a.L, a.H, a.p, a.seed, a.sid,
+             b.dqkv, b.row_scale, b.row_min);
+  });
   if (rc) return rc;
-  const Shape kv = dkv_shape(sh);
-  if (kv == W8) return launch_dkv<DK, 8, 1>(qkv, seq, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
-  if (kv == W4) return launch_dkv<DK, 4, 1>(qkv, seq, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
-  return launch_dkv<DK, 4, 2>(qkv, seq, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
+  return by_shape<DKV, DK>(pl.dkv, a, [&](auto t) {
+    const bool bits = b.keep_bits && a.p > 0.f;
+    return t(bits ? attn_bwd_dkv_f16x2_kernel<DK, t.NW, t.PARTS, true> : attn_bwd_dkv_f16x2_kernel<DK, t.NW, t.PARTS, false>, a.qkv,
+             a.seq, b.d_o, b.lse, b.delta, a.L, a.H, a.p, a.seed, a.sid, b.dqkv, b.row_scale, b.row_min,
+             bits ? b.keep_bits : nullptr);
+  });
+}
+
+// The one-sweep backward pass (head size 64), unsplit or split: delta, the sweep, and the sum of the slabs of a split one.
+// Pre-split K / V only where the 256-query forward kernel reads them too: one workgroup per key block, no query ranges (plan()).
+using Sweep = decltype(&attn_bwd_fused_f16x2_kernel<false, false, 0>);
+template <bool KVP, int SPLIT>
+Sweep sweep_kernel(bool bits) {
+  return bits ? attn_bwd_fused_f16x2_kernel<true, KVP, SPLIT> : attn_bwd_fused_f16x2_kernel<false, KVP, SPLIT>;
+}
+int launch_sweep(const Plan &pl, const AttnArgs &a, const AttnBwd &b, const AttnKv &kv) {
+  const size_t items = (size_t)a.B * a.L * a.H * 16, T = (size_t)a.B * a.L;
+  const int D = a.H * 64;
+  if (int rc = attn_launch(attn_delta_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, a.stream, b.o_fwd, b.d_o,
+                           a.B * a.L, a.L, a.H, 64, b.delta))
+    return rc;
+  const bool split = pl.bwd == BWD_SPLIT, ranges = pl.qs > 1, bits = b.keep_bits && a.p > 0.f, kvp = kv.planes != nullptr;
+  const Sweep kern = !split ? (kvp ? sweep_kernel<true, 0>(bits) : sweep_kernel<false, 0>(bits))
+                     : ranges ? sweep_kernel<false, 2>(bits)
+                     : kvp    ? sweep_kernel<true, 1>(bits)
+                              : sweep_kernel<false, 1>(bits);
+  float *dq_part = split ? b.slabs : nullptr, *dkv_part = split ? b.slabs + (size_t)pl.nkb * T * D : nullptr;
+  const int rc = attn_launch(kern, dim3(split ? pl.nkb * pl.qs : 1, a.H, a.B), dim3(512), FUSED_LDS, a.stream, a.qkv, a.seq, b.d_o,
+                             b.lse, b.delta, a.L, a.H, a.p, a.seed, a.sid, b.dqkv, b.row_scale, b.row_min, b.keep_bits, kv.planes,
+                             kv.inv, (a.B * a.L) / 32, dq_part, dkv_part, pl.qs);
+  if (rc || !split) return rc;
+  return attn_launch(ranges ? attn_bwd_split_reduce_kernel<true> : attn_bwd_split_reduce_kernel<false>, dim3((unsigned)((T + 7) / 8)),
+                     dim3(256), 0, a.stream, dq_part, pl.nkb, dkv_part, pl.qs, T, D, b.dqkv, b.row_scale, b.row_min);
 }
 }  // namespace
 }  // namespace ptattn16
 
 bool pt_attention_f16x2_reads_kv_planes(int B, int L, int H, int dk) { return ptattn16::plan(B, L, H, dk).kv_planes; }
-
-int pt_attention_fwd_f16x2(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float p, uint64_t seed,
-                           uint32_t sid, float *out, float *lse, uint32_t *keep_bits, const void *kv_planes, const float *kv_inv,
-                           hipStream_t st) {
-  using namespace ptattn16;
-  const Plan pl = plan(B, L, H, dk);
-  if (kv_planes) {
-    if (!kv_inv || !pl.kv_planes) return PTAMD_ERR_BAD_SHAPE;
-    return launch_fwd_kvp(qkv, static_cast<const char *>(kv_planes), kv_inv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  }
-  if (dk == 128) return fwd_by_plan<128>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-  return dk == 64 ? fwd_by_plan<64>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st)
-                  : fwd_by_plan<32>(pl, qkv, seq, B, L, H, p, seed, sid, out, lse, keep_bits, st);
-}
-
-// (the one-sweep kernel and, on the two-kernel path, the dK / dV kernel - both keep keys in lanes; the dQ kernel draws them)
-bool pt_attention_bwd_f16x2_reads_keep_bits(int B, int L, int H, int dk) {
-  return B > 0 && L > 0 && H > 0 && (dk == 64 || dk == 32 || dk == 128);
-}
 
 // floats of workspace the f16x2 backward pass of this shape wants BEHIND delta (the slabs of the split sweep; 0 otherwise)
 size_t pt_attention_bwd_f16x2_slab_floats(int B, int L, int H, int dk) {
@@ -2036,27 +1954,30 @@ size_t pt_attention_bwd_f16x2_slab_floats(int B, int L, int H, int dk) {
   return split_floats(B, L, H, plan(B, L, H, dk));
 }
 
-int pt_attention_bwd_f16x2(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
-                           float *delta, int B, int L, int H, int dk, float p, uint64_t seed, uint32_t sid, float *dqkv,
-                           uint32_t *row_scale, uint32_t *row_min, const uint32_t *keep_bits, const void *kv_planes,
-                           const float *kv_inv, float *slabs, size_t slab_floats, hipStream_t st) {
+int pt_attention_fwd_f16x2(const AttnArgs &a, const AttnFwd &f, const AttnKv &kv) {
   using namespace ptattn16;
-  const Plan pl = plan(B, L, H, dk);
-  if (kv_planes && (!kv_inv || !pl.kv_planes)) return PTAMD_ERR_BAD_SHAPE;
-  // (the forward kernel's decisions are read by the fused kernel and by the dK / dV kernel of the two-kernel path)
-  if (pl.bwd == BWD_SWEEP)
-    return launch_fused(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
-                        static_cast<const char *>(kv_planes), kv_inv, st);
-  if (pl.bwd == BWD_SPLIT) {
-    if (!slabs || slab_floats < split_floats(B, L, H, pl)) return PTAMD_ERR_WORKSPACE;
-    return launch_fused_split(pl, qkv, seq, o_fwd, d_o, lse, delta, slabs, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits,
-                              static_cast<const char *>(kv_planes), kv_inv, st);
+  const Plan pl = plan(a.B, a.L, a.H, a.dk);
+  if (kv.planes) {
+    if (!kv.inv || !pl.kv_planes) return PTAMD_ERR_BAD_SHAPE;
+    return attn_launch(attn_fwd_kvp_f16x2_kernel, dim3((a.L + 255) / 256, a.H, a.B), dim3(512), KvpGeo::LDS, a.stream, a.qkv,
+                       kv.planes, kv.inv, (a.B * a.L) / 32, a.seq, a.L, a.H, a.p, a.seed, a.sid, f.out, f.lse, f.keep_bits);
   }
-  if (dk == 128) {  // (W4 for both kernels whatever the forward shape)
-    const int rc = launch_dq<128, 4, 1>(qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, st);
-    if (rc) return rc;
-    return launch_dkv<128, 4, 1>(qkv, seq, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
-  }
-  return dk == 64 ? bwd_by_shape<64>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st)
-                  : bwd_by_shape<32>(pl.shape, qkv, seq, o_fwd, d_o, lse, delta, B, L, H, p, seed, sid, dqkv, row_scale, row_min, keep_bits, st);
+  // 8 wavefronts as 2 query groups x 4 key quarters on unpadded tiles (round 6; head size 64): as many workgroups as 4 x (2 x 2)
+  // - 64 queries each - with HALF the tile loop per wavefront and TWO wavefronts per SIMD (one wavefront per SIMD runs a tile in
+  // 3.3 us, two in 1.5 each: the forward pass of the 4-protein share)
+  if (pl.quarters)
+    return attn_launch(attn_fwd_f16x2_kernel<64, 8, 4, Tile2U>, dim3((a.L + 63) / 64, a.H, a.B), dim3(512),
+                       (size_t)4 * 2 * (2 * Tile2U::ELEMS) * sizeof(unsigned short), a.stream, a.qkv, a.seq, a.L, a.H, a.p, a.seed,
+                       a.sid, f.out, f.lse, f.keep_bits);
+  return attn_by_dk<128, 64, 32>(a.dk, [&](auto DK) { return launch_fwd<decltype(DK)::value>(pl, a, f); });
+}
+
+int pt_attention_bwd_f16x2(const AttnArgs &a, const AttnBwd &b, const AttnKv &kv) {
+  using namespace ptattn16;
+  const Plan pl = plan(a.B, a.L, a.H, a.dk);
+  if (kv.planes && (!kv.inv || !pl.kv_planes)) return PTAMD_ERR_BAD_SHAPE;
+  if (pl.bwd == BWD_TWO_KERNELS)
+    return attn_by_dk<128, 64, 32>(a.dk, [&](auto DK) { return launch_two_kernels<decltype(DK)::value>(pl, a, b); });
+  if (pl.bwd == BWD_SPLIT && (!b.slabs || b.slab_floats < split_floats(a.B, a.L, a.H, pl))) return PTAMD_ERR_WORKSPACE;
+  return launch_sweep(pl, a, b, kv);
 }

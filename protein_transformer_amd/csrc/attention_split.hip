@@ -12,8 +12,8 @@
 // MFMA accumulator layout, is split in registers and fed straight back as the B operand of O^T += V^T P^T.
 // K and V tiles of 32 keys are staged once per workgroup as three bf16 planes each in the swizzled LDS format of
 // split_bf16.h, which serves the row-fragment reads (K in QK^T) and the transposed reads (V^T in PV) conflict-free.
+#include "attention_internal.h"
 #include "attn_dropout.h"
-#include "split_bf16.h"
 
 namespace ptattn {
 using namespace ptsplit;
@@ -22,9 +22,6 @@ constexpr int NTHR = 512;        // 8 wavefronts: a staged tile is converted onc
 constexpr int QB = NTHR / 2;     // queries (or keys) per workgroup: 32 per wavefront
 constexpr int TR = 32;  // rows (keys or queries) of an LDS tile
 typedef Tile64<TR> Tile;
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // 32 rows x 64 floats of a [*, ld] matrix, global -> registers -> split planes in LDS (512 threads, 1 float4 each).
 // The loads are unconditional (row clamped); rows beyond nrows are zeroed when they are stored.
@@ -485,50 +482,24 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
-template <typename Kern>
-int set_lds(Kern kern) {
-  PT_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)ATTN_LDS));
-  return PTAMD_OK;
-}
-
 }  // namespace ptattn
 
-int pt_attention_fwd_split(const float *qkv, const int64_t *seq, int B, int L, int H, int dk, float p, uint64_t seed,
-                           uint32_t sid, float *out, float *lse, hipStream_t st) {
+int pt_attention_fwd_split(const AttnArgs &a, const AttnFwd &f) {
   using namespace ptattn;
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  if (dk == 64) {
-    if (int rc = set_lds(attn_fwd_split_kernel<64>)) return rc;  // idempotent, host-only: no state kept between calls
-    hipLaunchKernelGGL(attn_fwd_split_kernel<64>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, L, H, p, seed, sid, out, lse);
-  } else {
-    if (int rc = set_lds(attn_fwd_split_kernel<32>)) return rc;
-    hipLaunchKernelGGL(attn_fwd_split_kernel<32>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, L, H, p, seed, sid, out, lse);
-  }
-  return pt_check_launch();
+  return attn_by_dk<64, 32>(a.dk, [&](auto DK) {
+    return attn_launch(attn_fwd_split_kernel<decltype(DK)::value>, dim3((a.L + QB - 1) / QB, a.H, a.B), dim3(NTHR), ATTN_LDS,
+                       a.stream, a.qkv, a.seq, a.L, a.H, a.p, a.seed, a.sid, f.out, f.lse);
+  });
 }
 
-int pt_attention_bwd_split(const float *qkv, const int64_t *seq, const float *o_fwd, const float *d_o, const float *lse,
-                           float *delta, int B, int L, int H, int dk, float p, uint64_t seed, uint32_t sid, float *dqkv,
-                           hipStream_t st) {
+int pt_attention_bwd_split(const AttnArgs &a, const AttnBwd &b) {
   using namespace ptattn;
-  const dim3 grid((L + QB - 1) / QB, H, B);
-  if (dk == 64) {
-    if (int rc = set_lds(attn_bwd_dq_split_kernel<64>)) return rc;
-    if (int rc = set_lds(attn_bwd_dkv_split_kernel<64>)) return rc;
-    hipLaunchKernelGGL(attn_bwd_dq_split_kernel<64>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, o_fwd, d_o, lse, delta, L, H, p,
-                       seed, sid, dqkv);
-    if (int rc = pt_check_launch()) return rc;
-    hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<64>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed,
-                       sid, dqkv);
-  } else {
-    if (int rc = set_lds(attn_bwd_dq_split_kernel<32>)) return rc;
-    if (int rc = set_lds(attn_bwd_dkv_split_kernel<32>)) return rc;
-    hipLaunchKernelGGL(attn_bwd_dq_split_kernel<32>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, o_fwd, d_o, lse, delta, L, H, p,
-                       seed, sid, dqkv);
-    if (int rc = pt_check_launch()) return rc;
-    hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<32>, grid, dim3(NTHR), ATTN_LDS, st, qkv, seq, d_o, lse, delta, L, H, p, seed,
-                       sid, dqkv);
-  }
-  return pt_check_launch();
+  return attn_by_dk<64, 32>(a.dk, [&](auto DK) {
+    const dim3 grid((a.L + QB - 1) / QB, a.H, a.B);
+    if (int rc = attn_launch(attn_bwd_dq_split_kernel<decltype(DK)::value>, grid, dim3(NTHR), ATTN_LDS, a.stream, a.qkv, a.seq,
+                             b.o_fwd, b.d_o, b.lse, b.delta, a.L, a.H, a.p, a.seed, a.sid, b.dqkv))
+      return rc;
+    return attn_launch(attn_bwd_dkv_split_kernel<decltype(DK)::value>, grid, dim3(NTHR), ATTN_LDS, a.stream, a.qkv, a.seq, b.d_o,
+                       b.lse, b.delta, a.L, a.H, a.p, a.seed, a.sid, b.dqkv);
+  });
 }

@@ -1,5 +1,6 @@
 // Dropout on the attention probabilities (Attention.py:16-22 of the reference: nn.Dropout(0.1) on softmax(QK^T)),
-// shared by attention.hip and attention_split.hip so that every kernel of both arithmetic modes draws the same mask.
+// shared by attention.hip, attention_split.hip and attention_f16x2.hip so that every kernel of all three arithmetic families
+// draws the same mask.
 //
 // One 32-bit word of the counter hash pt_mix32 (common.h) serves a PAIR of adjacent keys of one query: the even key
 // is decided by its low 16 bits, the odd key by its high 16 bits, against a 16-bit threshold.  The kernels that keep a
