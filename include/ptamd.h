@@ -138,6 +138,30 @@ int ptamd_drmsd_bb_fwd_bwd_budget(const float *pred_bb, const float *true_crd, c
 int ptamd_kabsch_rmsd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *rmsd,
                       void *stream);
 
+/* lDDT, all-atom and C-alpha, for a whole batch (csrc/lddt.hip).  The reference has no counterpart - its evaluation stops at
+ * dRMSD and the superposed RMSD; this is the score of Mariani, Biasini, Barbato & Schwede, "lDDT: a local superposition-free
+ * score for comparing protein structures and models using distance difference tests", Bioinformatics 29(21):2722-2728 (2013),
+ * without the stereochemistry checks of the full tool.
+ *   pred_crd, true_crd [B,L*14,3], seq [B,L]: as for ptamd_kabsch_rmsd - the atoms of a protein are the slots s of residues
+ *   other than PTAMD_PAD_ID whose true coordinate has no NaN; an atom's residue is s / 14.
+ *   An ordered pair (i, j) of atoms in DIFFERENT residues is included if its true distance dt < cutoff (the usual cutoff is
+ *   15 A) and preserved at t in {0.5, 1, 2, 4} A if |dp - dt| < t, dp the predicted distance; both comparisons are strict, both
+ *   distances are sqrt(dx^2 + dy^2 + dz^2) of coordinate differences in fp32.  A non-finite predicted coordinate fails the
+ *   comparisons, nothing traps.
+ *   counts [B,L,2,5] out: per residue r and atom set (0: every atom; 1: C-alpha = slot 1, paired with C-alphas only)
+ *   {total, p0.5, p1, p2, p4} over the included pairs whose i lies in r; zero-filled by the call itself, zeros for padded
+ *   residues and residues without a present atom.
+ *   per_res [B,L,2] out: (p0.5 + p1 + p2 + p4) / (4 total), NaN where total == 0.
+ *   score [B,2] out: the same ratio of the 64-bit sums over the protein's residues, NaN without an included pair.
+ * Integer counters and integer atomics only: the same bits whatever the scheduling, and a protein's counts do not depend on
+ * the batch around it.  Workspace: 32 B per atom slot (the present atoms compacted in slot order) + 32 B per tile of 64 of them
+ * (bounding boxes) - a function of (B, L) only.  cutoff not finite and positive, a NULL array, B or L <= 0 (or L beyond
+ * INT_MAX / 28): PTAMD_ERR_BAD_SHAPE; workspace NULL or too small: PTAMD_ERR_WORKSPACE; nothing is launched or written then.
+ * No length limit otherwise, no state between calls, nothing read from the environment. */
+size_t ptamd_lddt_workspace_bytes(int B, int L);
+int ptamd_lddt(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff,
+               int32_t *counts, float *per_res, float *score, void *workspace, size_t workspace_bytes, void *stream);
+
 /* mse_over_angles x3 (losses.py:175-214; train.py:64-66) in one pass.
  *   pred, truth [T,24]; out[6] = {sum_full, cnt_full, sum_bb, cnt_bb, sum_sc, cnt_sc} (fp32); the workspace holds
  *   the fp64 partial sums of the first pass */

@@ -1,4 +1,4 @@
-"""Eval-only RMSD after optimal superposition (Kabsch), SURVEY.md section 8f row 1.
+"""Eval-only metrics: RMSD after optimal superposition (Kabsch), SURVEY.md section 8f row 1, and lDDT (below).
 
 Reference: `rmsd` (/root/reference/protein_transformer/losses.py:281-286) calls ProDy's
 calcTransformation / calcRMSD, reached only from `eval_epoch` (train.py:125-127) with
@@ -6,6 +6,10 @@ return_rmsd=True.  ProDy is not installable here, so this is the textbook Kabsch
 (PARITY UNPINNED, same caveat as oracle/losses.py:kabsch_rmsd).  It runs as ONE kernel launch per batch
 (csrc/kabsch.hip: fp64 moments per protein, Jacobi eigenvalues of H^T H on the device) - no per-protein host
 round trip, no torch.linalg.
+
+lDDT (`lddt_batch`, `batch_lddt`; `train.py --eval_lddt`) has no counterpart in the reference: Mariani et al., Bioinformatics
+29(21):2722-2728 (2013), all-atom and C-alpha, per residue and per protein, counted on the device (csrc/lddt.hip; definition in
+include/ptamd.h).
 """
 import numpy as np
 import torch
@@ -24,6 +28,32 @@ def kabsch_rmsd_batch(pred_crd, true_crd, seq):
                                       _lib.ptr(seq.contiguous()), B, L, _lib.ptr(out), _lib.stream())
     _lib.check(rc, "kabsch_rmsd")
     return out
+
+
+def lddt_batch(pred_crd, true_crd, seq, cutoff=15.0):
+    """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] ->
+    (score [B,2], per_res [B,L,2], counts [B,L,2,5] int32), all on the device, no sync.  Last-but-one axis / `score` columns:
+    0 = every atom, 1 = C-alpha only; counts = {total, p0.5, p1, p2, p4} per residue (include/ptamd.h); NaN = no included pair."""
+    _lib.require_gpu(pred_crd, true_crd, seq)
+    B, L = seq.shape
+    assert pred_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crd.shape == pred_crd.shape
+    dev = seq.device
+    counts = torch.empty(B, L, 2, 5, dtype=torch.int32, device=dev)       # zero-filled by the entry point
+    per_res = torch.empty(B, L, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("lddt", _lib.lib().ptamd_lddt_workspace_bytes(B, L), dev)
+    rc = _lib.lib().ptamd_lddt(_lib.ptr(pred_crd.float().contiguous()), _lib.ptr(true_crd.float().contiguous()),
+                               _lib.ptr(seq.contiguous()), B, L, float(cutoff), _lib.ptr(counts), _lib.ptr(per_res),
+                               _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "lddt")
+    return score, per_res, counts
+
+
+def lddt_sums(score):
+    """score [B,2] -> device fp64 [4] = (sum of the finite lddt-full, sum of the finite lddt-ca, their two counts): what
+    losses.LossReport carries, so that the mean over the proteins WITH a score can be formed over a global batch."""
+    ok = torch.isfinite(score)
+    return torch.cat([torch.where(ok, score, torch.zeros_like(score)).double().sum(0), ok.double().sum(0)])
 
 
 def rmsd(a, b):
@@ -47,3 +77,15 @@ def batch_rmsd(pred_sincos, true_crds, input_seqs):
     ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
     crd, _ = nerf_forward(ang, input_seqs)
     return float(kabsch_rmsd_batch(crd, true_crds, input_seqs).double().mean())
+
+
+def batch_lddt(pred_sincos, true_crds, input_seqs, cutoff=15.0):
+    """(lddt-full, lddt-ca): means over the proteins with a finite score of the lDDT of the structures built from
+    pred_sincos (NaN when no protein has one); one host read."""
+    from .losses import angles_forward
+    from .protein.Structure import nerf_forward
+    B, L = input_seqs.shape
+    ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
+    crd, _ = nerf_forward(ang, input_seqs)
+    s = lddt_sums(lddt_batch(crd, true_crds, input_seqs, cutoff)[0]).cpu().numpy()
+    return tuple(float(s[k] / s[2 + k]) if s[2 + k] > 0 else float("nan") for k in range(2))

@@ -19,6 +19,9 @@ from .protein.Sequence import VOCAB
 _TRACKED = ("drmsd-full", "lndrmsd-full", "mse-full", "combined-full", "rmsd-full", "drmsd-bb", "lndrmsd-bb",
             "mse-bb", "mse-sc")
 _HISTORY = ("drmsd", "combined", "lndrmsd", "mse")
+# evaluation under `train.py --eval_lddt` only (no counterpart in the reference): present in a split's metrics once a batch has
+# reported them, as sum-<k> / n-<k> over the batches with a finite value and epoch-<k> = their mean
+_LDDT = ("lddt-full", "lddt-ca")
 
 
 class EarlyStoppingCondition(Exception):
@@ -49,6 +52,9 @@ def reset_metrics_for_epoch(metrics, mode):
     m = metrics.setdefault(mode, _split_metrics())
     for k in _TRACKED:
         m[f"epoch-{k}"] = m[f"batch-{k}"] = 0
+    for k in _LDDT:
+        for prefix in ("epoch", "sum", "n"):
+            m.pop(f"{prefix}-{k}", None)
     m["batch-history"], m["speed-history"] = [], []
     m["batch-time"] = time.time()
     metrics["n_batches"] = 0
@@ -67,6 +73,11 @@ def update_metrics(metrics, losses, mode, src_seq, tracking_loss=None, batch_lev
             m[f"epoch-{k}"] += v
         else:
             m[f"epoch-{k}"] = v                       # the reference overwrites the bb/sc entries (log.py:413-416)
+    for k in _LDDT:
+        if k in losses:                               # a batch without any scored protein reports NaN and is left out
+            v = _num(losses[k])
+            m[f"sum-{k}"] = m.get(f"sum-{k}", 0.0) + (v if np.isfinite(v) else 0.0)
+            m[f"n-{k}"] = m.get(f"n-{k}", 0) + int(np.isfinite(v))
     # residues of the GLOBAL batch: counted on the host before the upload and reduced with the loss statistics
     # (losses.LossReport); the device count is only the fall-back for callers that did not pass one
     num_res = losses.get("n-residues")
@@ -88,6 +99,9 @@ def update_metrics_end_of_epoch(metrics, mode):
     for k in ("drmsd-full", "lndrmsd-full", "mse-full", "drmsd-bb", "lndrmsd-bb", "mse-bb", "mse-sc", "rmsd-full"):
         m[f"epoch-{k}"] /= n
     m["epoch-combined-full"] = 0 if m["epoch-drmsd-full"] == 0 else m["epoch-combined-full"] / n
+    for k in _LDDT:
+        if f"n-{k}" in m:
+            m[f"epoch-{k}"] = m[f"sum-{k}"] / m[f"n-{k}"] if m[f"n-{k}"] else float("nan")
     for h in _HISTORY:
         m[f"epoch-history-{h}"].append(m[f"epoch-{h}-full"])
     return metrics
@@ -111,25 +125,30 @@ REFERENCE_CSV = False     # True: the granularity column carries upstream's lite
 
 
 def prepare_log_header(args):
+    tail = ',lddt,lddt_ca' if getattr(args, "eval_lddt", False) else ''      # two trailing columns under --eval_lddt only
     if args.loss == "combined":
-        return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed'
-    return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed'
+        return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed' + tail
+    return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed' + tail
 
 
-def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None):
+def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False):
     """One CSV row (log.py:115-130): ten values - drmsd, ln_drmsd, rmse, rmsd, combined, lr, mode, granularity, time,
     speed; like upstream the `combined` value is written whatever the header of `prepare_log_header` lists.  One
     deliberate difference: the granularity column says "batch" for per-batch rows (upstream writes the literal "epoch"
     in both cases, log.py:130) - unless `REFERENCE_CSV` is set (`train.py --reference-csv`), which reproduces the
-    upstream column byte for byte for consumers of the reference's `.train` files."""
+    upstream column byte for byte for consumers of the reference's `.train` files.  `lddt` (`train.py --eval_lddt`): two
+    trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it)."""
     t = t or time.time()
     m = metrics[mode]
     be = "epoch" if end_of_epoch else "batch"
     label = "epoch" if REFERENCE_CSV else be
     lr = metrics["history-lr"][-1] if metrics["history-lr"] else 0
-    log_writer.writerow([m[f"{be}-drmsd-full"], m[f"{be}-lndrmsd-full"], np.sqrt(m[f"{be}-mse-full"]),
-                         m[f"{be}-rmsd-full"], m[f"{be}-combined-full"], lr, mode, label, round(t - start_time, 4),
-                         m.get("speed", 0)])
+    row = [m[f"{be}-drmsd-full"], m[f"{be}-lndrmsd-full"], np.sqrt(m[f"{be}-mse-full"]),
+           m[f"{be}-rmsd-full"], m[f"{be}-combined-full"], lr, mode, label, round(t - start_time, 4),
+           m.get("speed", 0)]
+    if lddt:
+        row += [m.get(f"{be}-{k}", float("nan")) for k in _LDDT]
+    log_writer.writerow(row)
 
 
 def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer, start_time, step):
@@ -140,7 +159,7 @@ def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer
     lr = optimizer.param_groups[0]["lr"]
     metrics["history-lr"].append(lr)
     if dp.is_main():
-        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False)
+        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)))
         if step % max(1, getattr(args, "log_wandb_step", 1) * 10) == 0:
             m = metrics["train"]
             print(f"  step {step:5d}  drmsd {m['batch-drmsd-full']:.4f}  ln {m['batch-lndrmsd-full']:.6f}  "
@@ -184,5 +203,6 @@ def do_eval_epoch_logging(metrics, mode):
     update_metrics_end_of_epoch(metrics, mode)
     if dp.is_main():
         m = metrics[mode]
+        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _LDDT if f"epoch-{k}" in m)      # --eval_lddt only
         print(f"  [{mode}] drmsd {m['epoch-drmsd-full']:.4f}  ln {m['epoch-lndrmsd-full']:.6f}  "
-              f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}", flush=True)
+              f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}{tail}", flush=True)

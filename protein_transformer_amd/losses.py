@@ -201,16 +201,18 @@ class LossReport:
 
     # [0:4] sums of drmsd, ln, bb, bb-ln  [4] proteins  [5] sum rmsd  [6:12] mse sums  [12:16] status bits  [16] residues
     # [17] proteins with rmsd  [18] ranks that passed a residue count (0: nobody counted - n_res stays None like on one rank)
-    _NVEC = 19
+    # [19:21] sums of the finite lddt-full, lddt-ca  [21:23] proteins with a finite lddt-full, lddt-ca (--eval_lddt; else 0)
+    _NVEC = 23
 
-    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None):
+    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None):
+        """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None."""
         from . import dp
         self.world = dp.world_size()
         self.n_res = n_res
         if self.world == 1:
             B = 0 if stats is None else stats.shape[0]
             self._B = B
-            n = B * 8 + 6 + 1 + B
+            n = B * 8 + 6 + 1 + B + (2 * B if lddt is not None else 0)
             buf = _pinned("report32", n, torch.float32, device)
             if stats is not None:
                 buf[:B * 8].copy_(stats.reshape(-1), non_blocking=True)
@@ -219,8 +221,11 @@ class LossReport:
             if status is not None:       # raw int32 bits into the float slot
                 buf.view(torch.int32)[B * 8 + 6:B * 8 + 7].copy_(status, non_blocking=True)
             if rmsd is not None:
-                buf[B * 8 + 7:].copy_(rmsd, non_blocking=True)
+                buf[B * 8 + 7:B * 9 + 7].copy_(rmsd, non_blocking=True)
+            if lddt is not None:
+                buf[B * 9 + 7:].copy_(lddt.reshape(-1), non_blocking=True)
             self._has = (stats is not None, mse_sums_local is not None, status is not None, rmsd is not None)
+            self._has_lddt = lddt is not None
             self._buf = buf
             self.global_mse_sums = mse_sums_local
         else:
@@ -237,6 +242,9 @@ class LossReport:
                 v[12:16] = ((status.to(torch.int64) >> torch.arange(4, device=device)) & 1).double()
             v[16] = float(n_res or 0)
             v[18] = 0.0 if n_res is None else 1.0
+            if lddt is not None:
+                from .eval_metrics import lddt_sums
+                v[19:23] = lddt_sums(lddt)
             dp.all_reduce_sum_(v)
             self.global_mse_sums = v[6:12].float()
             buf = _pinned("report64", self._NVEC, torch.float64, device)
@@ -249,7 +257,7 @@ class LossReport:
         """Block until the copies have landed; returns a dict of host numbers (float64 / int)."""
         self._event.synchronize()
         out = {"drmsd": 0.0, "lndrmsd": 0.0, "drmsd-bb": 0.0, "lndrmsd-bb": 0.0, "rmsd": None, "n_proteins": 0,
-               "status": 0, "n_res": self.n_res, "mse": None}
+               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None}
         if self.world == 1:
             B = self._B
             host = self._buf.numpy()
@@ -263,7 +271,12 @@ class LossReport:
             if has_status:
                 out["status"] = int(host[B * 8 + 6:B * 8 + 7].view(np.int32)[0])
             if has_rmsd and B:
-                out["rmsd"] = float(np.mean(host[B * 8 + 7:].astype(np.float64)))
+                out["rmsd"] = float(np.mean(host[B * 8 + 7:B * 9 + 7].astype(np.float64)))
+            if self._has_lddt:
+                sc = host[B * 9 + 7:].reshape(B, 2).astype(np.float64)
+                for k, name in enumerate(("lddt", "lddt-ca")):       # mean over the proteins with a score
+                    ok = np.isfinite(sc[:, k])
+                    out[name] = float(sc[ok, k].mean()) if ok.any() else float("nan")
         else:
             v = self._buf.numpy().copy()
             n = max(v[4], 1.0)
@@ -273,6 +286,8 @@ class LossReport:
                         "n_res": int(v[16]) if v[18] > 0 else None})
             if v[17] > 0:
                 out["rmsd"] = v[5] / v[17]
+            out["lddt"] = v[19] / v[21] if v[21] > 0 else float("nan")
+            out["lddt-ca"] = v[20] / v[22] if v[22] > 0 else float("nan")
         return out
 
 

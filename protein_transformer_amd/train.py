@@ -113,12 +113,17 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     (backbone chain kernels and a pair sweep over 3 L atoms only), so no full-atom dRMSD exists in it: the dictionary keeps its
     10 keys and `drmsd-full` / `lndrmsd-full` / `combined-full` carry the BACKBONE values there.  Evaluation (`eval_mode`) builds
     the whole structure and reports every metric as without the flag (`rmsd-full` needs all atoms); only `loss` follows the rule.
+
+    `args.eval_lddt` (no counterpart in the reference): in `eval_mode` the dictionary gains `lddt-full` and `lddt-ca`, the mean
+    lDDT (eval_metrics.lddt_batch, on the coordinates built for the dRMSD and `rmsd-full`) over the proteins of the global batch
+    that have a score.  Without the flag, and in every training step, nothing is computed and the keys are absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
     need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined"] or eval_mode
     backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
-    sums = stats = grad = status = rmsd = None
+    want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
+    sums = stats = grad = status = rmsd = lddt = None
     if not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
@@ -138,7 +143,10 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
                     crd, _ = nerf_forward(angles_forward(pred.detach().float().contiguous().view(*src_seq.shape, -1)), src_seq,
                                           status=status)
                 rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
-    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res)
+            if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
+                from .eval_metrics import lddt_batch
+                lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
+    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt)
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -174,6 +182,10 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     out = {"loss": loss, "drmsd-full": d_loss, "lndrmsd-full": ln_d_loss, "drmsd-bb": d_bb_loss,
            "lndrmsd-bb": d_bb_ln_loss, "combined-full": c_loss, "mse-full": m_loss_full, "mse-bb": m_loss_bb,
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
+    if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
+        nan = float("nan")
+        out["lddt-full"] = np.float64(host["lddt"] if host["lddt"] is not None else nan)
+        out["lddt-ca"] = np.float64(host["lddt-ca"] if host["lddt-ca"] is not None else nan)
     if host["n_res"] is not None:
         out["n-residues"] = host["n_res"]                      # residues of the GLOBAL batch (speed meter, log.py)
     return out
@@ -205,13 +217,13 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
         if args.eval_train:
             metrics = eval_epoch(model, train_eval_loader, device, args, metrics, mode="train", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True)
+            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
         if not args.train_only:
             for split, validation_data in validation_datasets.items():
                 metrics = eval_epoch(model, validation_data, device, args, metrics, mode=f"valid-{split}",
                                      pool=drmsd_worker_pool)
                 if dp.is_main():
-                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True)
+                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
         # every rank holds the same (globally reduced) metrics, so the scheduler, the early-stopping test and the
         # checkpoint policy below take the same branch on every rank
         if scheduler:
@@ -225,7 +237,7 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
     if not args.train_only and test_data is not None:
         metrics = eval_epoch(model, test_data, device, args, metrics, mode="test", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True)
+            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
     return metrics
 
 
@@ -489,6 +501,9 @@ def create_parser():
     training.add_argument("--batching_order", type=str, choices=["descending", "ascending", "binned-random"],
                           default="binned-random")
     training.add_argument('--backbone_loss', action='store_true')
+    training.add_argument('--eval_lddt', action='store_true',
+                          help="evaluation also reports lDDT, all-atom and C-alpha (Mariani et al. 2013; no counterpart in the "
+                               "reference): two more values on the per-epoch evaluation line, two trailing columns in the .train log")
     training.add_argument('--sequential_drmsd_loss', action="store_true")
     training.add_argument("--bins", type=int, default=-1)
     training.add_argument("--train_eval_downsample", type=float, default=.10)
