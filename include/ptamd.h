@@ -375,6 +375,7 @@ int ptamd_fill_u32(const ptamd_fill_job *jobs_host, int njobs, void *stream);
  * The description of the model is a PLAN whose tables live in DEVICE memory (built once by the caller):
  *   segs        the listed matrices (or vectors, rows = 1) of the flat parameter buffer, K-contiguous, row stride = cols,
  *               cols % 4 == 0 and cols <= 512 (wider ones as column panels, see rowmax_index); pairwise disjoint;
+ *               statistics entry [0] (largest row norm) of a panelled matrix is NOT computed (it stays 0): no bound job reads it;
  *   blocks_a    [nblocks_a][2] int32: (segment, block of 32 rows inside it) for the first nblocks_a_matrices entries, then
  *               (-(range + 1), block of ptamd_wprep_plain_floats_per_block() floats inside plain range `range`): the plain
  *               ranges [nplain][2] int64 (first element, elements) cover everything that is not a segment - segments + plain

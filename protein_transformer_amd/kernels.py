@@ -713,6 +713,7 @@ class WeightsPrep:
         idx = lambda view, base: -1 if view is None else view.storage_offset() - base.storage_offset()       # noqa: E731
         table, blocks_a, blocks_b, plain = [], [], [], []
         ncolmax = ncolsq = 0            # entries of the pool of maxima (column maxima, row maxima of panelled matrices) / of colsq
+        rownorm_recs, panelled_recs = set(), set()      # statistics records fed by whole rows / by panels (maximum only)
         pos = 0
         for s in segs:
             rows, cols, off = int(s["rows"]), int(s["cols"]), int(s["offset"])
@@ -734,6 +735,8 @@ class WeightsPrep:
             wide = npanels > 1
             if wide and (s.get("row_planes") is not None or int(s.get("stats_row0", 0)) != 0):
                 raise ValueError("ptamd_weights_prep: a matrix wider than 512 columns cannot have row planes or a statistics sub-range")
+            if stats >= 0:
+                (panelled_recs if wide else rownorm_recs).add(stats)
             colmax0 = ncolmax
             ncolmax += cols if want_cols else 0
             rowmax0 = -1
@@ -787,6 +790,11 @@ class WeightsPrep:
         for g, jobs in enumerate(groups):
             first, cn_first = len(bounds), len(cn_list)
             for j in jobs:
+                # entry [0] of a record (the largest row norm) is what `w_index` 0 and `ln_beta` read: panels do not compute it
+                norms_read = ([int(j["w"])] if int(j["w_index"]) == 0 else []) + [rec(j.get("ln_beta"))]
+                if any(n in panelled_recs and n not in rownorm_recs for n in norms_read):
+                    raise ValueError("ptamd_weights_prep: a bound job reads the row norm of a matrix wider than 512 columns, "
+                                     "which the pass does not compute")
                 bounds.append(WprepBound(ln_gamma_stats=rec(j.get("ln_gamma")), ln_beta_stats=rec(j.get("ln_beta")), w_stats=int(j["w"]),
                                          w_stat_index=int(j["w_index"]), bias_stats=rec(j.get("bias")),
                                          sqrt_d=float(j.get("sqrt_d", 0.0)), post_scale=float(j.get("post_scale", 1.0)),

@@ -629,8 +629,10 @@ class _TransformerBase(nn.Module):
                     cache["hpT_scales"] += [L["cs_2"]]
                     cache["hpT_outs"] += [L["hp_2t"]]
             # (csrc/wprep.hip keeps whole rows of <= 512 columns in registers and walks wider matrices as 512-column panels:
-            # widths above 512 that are not multiples of 512 - d_model 768, d_ff 1000 - take the separate launches below)
-            panels_ok = all(c <= 512 or c % 512 == 0 for c in (D, F))
+            # widths above 512 that are not multiples of 512 - d_ff 1000 - take the separate launches below; so does every
+            # d_model above 512 - 768, 1024: W_qkv's statistics over its W_v rows and the row planes of W_qkv and W_1, all D
+            # columns wide, are things a panelled matrix cannot have)
+            panels_ok = D <= 512 and (F <= 512 or F % 512 == 0)
             cache["prep"] = self._build_prep(cache, p, pa) if (F <= 2048 and D % 4 == 0 and F % 4 == 0 and panels_ok) else None
         need_planes = bool(cache["hp_mats"]) and bool(hp)
         if self.weights_prep and cache.get("prep") is not None:
