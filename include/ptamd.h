@@ -162,6 +162,44 @@ size_t ptamd_lddt_workspace_bytes(int B, int L);
 int ptamd_lddt(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff,
                int32_t *counts, float *per_res, float *score, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
+ * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
+ * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the
+ * four threshold tests of lDDT.  It departs from that algorithm in a temperature tau that divides the argument of the sigmoids
+ * (tau = 1 is AlphaFold 3's loss, tau -> 0 approaches 1 - the hard all-atom lDDT of ptamd_lddt).
+ *   Atoms and pairs.  Per protein, the atoms are exactly those of ptamd_lddt: slots of non-pad residues whose true coordinate
+ *   has no NaN; an atom's residue is slot / 14.  An unordered pair {a, b} of atoms in different residues is included if its true
+ *   distance dt < cutoff.  The comparison is strict; dt = sqrt(dx^2 + dy^2 + dz^2) of fp32 coordinate differences, as in
+ *   ptamd_lddt.  Inclusion depends on the truth only.
+ *   Pair score.  delta = |dp - dt|, with dp the predicted distance under the same clamp under the root that the dRMSD kernel
+ *   applies (1e-30 added to the squares).  eps(delta) = 1/4 sum over t in {0.5, 1, 2, 4} of sigma((t - delta) / tau), with sigma
+ *   the logistic function and tau > 0 the temperature.  AlphaFold 3 uses tau = 1.
+ *   Per-protein outputs.  score_i is the mean of eps over the included pairs; loss_i = 1 - score_i; npairs_i is the number of
+ *   included unordered pairs, as an exact 64-bit integer.  A protein without an included pair has loss_i = score_i = NaN,
+ *   npairs_i = 0 and an all-zero gradient.  It is left out of every mean, as the metric does.
+ *   Gradient.  dcrd = d(loss_i)/d(pred_crd).  For atom a: -(1 / npairs_i) sum_b eps'(delta) sign(dp - dt) (x_a - x_b) / dp, with
+ *   sign(0) = 0.  A prediction equal to the truth therefore gets an exactly zero gradient.  Empty slots and padded residues get
+ *   zeros.  A non-finite predicted coordinate does not trap: the pairs of that atom are counted, contribute eps = 0 and no
+ *   gradient - neither to the atom itself (its row of dcrd is zero) nor to its partners.  A finite coordinate beyond 1e18 in
+ *   magnitude is treated the same way (its squared differences would overflow fp32).
+ *   Batch.  The reported batch value is the mean over proteins with a score; the back-propagated quantity is the SUM over
+ *   proteins of loss_i - the convention of every other structural loss here (SURVEY A-7), which keeps data parallelism a plain
+ *   SUM all-reduce with no global count.
+ *   stats [B,2] out = {loss_i, score_i}; npairs [B] out (int64); dcrd [B,L*14,3] out, or NULL for the forward-only form (no
+ *   gradient work; the same bits in stats and npairs).
+ * No floating-point atomics and fixed-order partial sums: two runs give the same bits, and a protein's result depends neither on
+ * the batch around it nor on how far its row is padded.  Workspace: a function of (B, L) only - 32 B per atom slot, and the
+ * partial sums of the upper-triangle sweep over tiles of 64 compacted atoms: 1 KB per (row tile, chunk of 8 column tiles) and
+ * per (strip of 4 row tiles, column tile); B = 32, L = 512: 162e6 bytes.  No getenv, no state between calls.
+ * cutoff or temperature not finite and positive, a NULL array other than dcrd, B or L <= 0, or L beyond INT_MAX / 28 (the bound
+ * of ptamd_lddt): PTAMD_ERR_BAD_SHAPE; workspace NULL or too small: PTAMD_ERR_WORKSPACE; nothing is launched or written in
+ * either case.  (The arguments t / tau of the exponentials are carried as integer + fraction: any tau down to 1e-8 keeps the
+ * definition; below that the four sigmoids saturate towards a step at their thresholds.) */
+size_t ptamd_slddt_workspace_bytes(int B, int L);
+int ptamd_slddt_fwd_bwd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff,
+                        float temperature, float *stats, int64_t *npairs, float *dcrd, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
 /* mse_over_angles x3 (losses.py:175-214; train.py:64-66) in one pass.
  *   pred, truth [T,24]; out[6] = {sum_full, cnt_full, sum_bb, cnt_bb, sum_sc, cnt_sc} (fp32); the workspace holds
  *   the fp64 partial sums of the first pass */

@@ -88,6 +88,25 @@ def drmsd_forward_backward(pred_crd, true_crd, seq, need_grad=True, partial_budg
     return stats, dcrd
 
 
+# ----------------------------------------------------------------------------- smooth lDDT
+def slddt_forward_backward(crd, true_crds, seq, need_grad=True, cutoff=15.0, temperature=1.0):
+    """Smooth lDDT loss of a batch (csrc/slddt.hip; definition in include/ptamd.h; no counterpart in the reference).
+    crd, true_crds [B,L*14,3], seq [B,L].  Returns (stats [B,2] = {loss_i, score_i}, npairs [B] int64, d(loss_i)/d(crd) or None);
+    a protein without an included pair has NaN statistics, npairs 0 and a zero gradient.  No host synchronisation."""
+    _lib.require_gpu(crd, true_crds, seq)
+    B, L = seq.shape
+    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
+    npairs = torch.empty(B, dtype=torch.int64, device=seq.device)
+    dcrd = torch.empty_like(crd) if need_grad else None
+    ws = _lib.workspace("slddt", _lib.lib().ptamd_slddt_workspace_bytes(B, L), seq.device)
+    rc = _lib.lib().ptamd_slddt_fwd_bwd(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(seq), B, L, float(cutoff), float(temperature),
+                                        _lib.ptr(stats), _lib.ptr(npairs), _lib.ptr(dcrd), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "slddt_fwd_bwd")
+    return stats, npairs, dcrd
+
+
 class _DrmsdFn(torch.autograd.Function):
     """drmsd(a, b) for two [n,3] point sets, differentiable in a."""
 
@@ -146,7 +165,7 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
     return generate_coords(angles, seq)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False):
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None):
     """Device-resident core of compute_batch_drmsd: no host synchronisation.
 
     Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
@@ -156,18 +175,33 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     side-chain builder, the pair sweep over 3 L atoms per protein.  stats[:, 2], [:, 3], [:, 5] (mirrored in [:, 0], [:, 1],
     [:, 4]) are the backbone numbers of the full call, the gradient is d(sum_i lndrmsd-bb_i)/d(pred_sincos) - exactly zero in the
     side-chain channels - and the coordinates of `return_crd` are the compact [B, L*3, 3] backbone.
+
+    `slddt` = (cutoff, temperature) (`train.py -l slddt`; None: everything above is unchanged): the structure is trained on the
+    smooth lDDT loss instead - angles -> NeRF forward -> smooth lDDT -> NeRF adjoint -> angles adjoint.  The gradient is
+    d(sum_i slddt_i)/d(pred_sincos), `stats` are still the dRMSD statistics (taken forward-only on the same coordinates, so logs
+    stay comparable between runs), and the per-protein smooth-lDDT losses [B] (NaN for a protein without an included pair) are
+    appended to the returned tuple as its last value.
     """
+    if slddt is not None:
+        assert not backbone_only, "the smooth lDDT loss is an all-atom loss"
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
     crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
-    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward, backbone_only=backbone_only)
+    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward and slddt is None,
+                                         backbone_only=backbone_only)
+    sl = None
+    if slddt is not None:
+        sl_stats, _, dcrd = slddt_forward_backward(crd, true_crds, input_seqs, need_grad=do_backward, cutoff=slddt[0],
+                                                   temperature=slddt[1])
+        sl = sl_stats[:, 0]
     grad = None
     if do_backward:
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
-    return (stats, grad, status, crd) if return_crd else (stats, grad, status)
+    out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
+    return out if slddt is None else out + (sl,)
 
 
 # ----------------------------------------------------------------------------- statistics hand-over
@@ -202,17 +236,20 @@ class LossReport:
     # [0:4] sums of drmsd, ln, bb, bb-ln  [4] proteins  [5] sum rmsd  [6:12] mse sums  [12:16] status bits  [16] residues
     # [17] proteins with rmsd  [18] ranks that passed a residue count (0: nobody counted - n_res stays None like on one rank)
     # [19:21] sums of the finite lddt-full, lddt-ca  [21:23] proteins with a finite lddt-full, lddt-ca (--eval_lddt; else 0)
-    _NVEC = 23
+    # [23] sum of the finite smooth-lDDT losses  [24] proteins with one (-l slddt; else 0)
+    _NVEC = 25
 
-    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None):
-        """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None."""
+    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None, slddt=None):
+        """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
+        `slddt`: per-protein smooth-lDDT losses [B] of batch_loss(..., slddt=...) (`-l slddt`) or None."""
         from . import dp
         self.world = dp.world_size()
         self.n_res = n_res
         if self.world == 1:
             B = 0 if stats is None else stats.shape[0]
             self._B = B
-            n = B * 8 + 6 + 1 + B + (2 * B if lddt is not None else 0)
+            n_lddt = 2 * B if lddt is not None else 0
+            n = B * 8 + 6 + 1 + B + n_lddt + (B if slddt is not None else 0)
             buf = _pinned("report32", n, torch.float32, device)
             if stats is not None:
                 buf[:B * 8].copy_(stats.reshape(-1), non_blocking=True)
@@ -223,7 +260,10 @@ class LossReport:
             if rmsd is not None:
                 buf[B * 8 + 7:B * 9 + 7].copy_(rmsd, non_blocking=True)
             if lddt is not None:
-                buf[B * 9 + 7:].copy_(lddt.reshape(-1), non_blocking=True)
+                buf[B * 9 + 7:B * 9 + 7 + n_lddt].copy_(lddt.reshape(-1), non_blocking=True)
+            if slddt is not None:
+                buf[B * 9 + 7 + n_lddt:].copy_(slddt.reshape(-1), non_blocking=True)
+            self._has_slddt, self._n_lddt = slddt is not None, n_lddt
             self._has = (stats is not None, mse_sums_local is not None, status is not None, rmsd is not None)
             self._has_lddt = lddt is not None
             self._buf = buf
@@ -245,6 +285,11 @@ class LossReport:
             if lddt is not None:
                 from .eval_metrics import lddt_sums
                 v[19:23] = lddt_sums(lddt)
+            if slddt is not None:
+                ok = torch.isfinite(slddt)
+                v[23] = torch.where(ok, slddt, torch.zeros_like(slddt)).double().sum()
+                v[24] = ok.sum()
+            self._has_slddt = slddt is not None       # (a rank with an empty shard passes None and reads the global value)
             dp.all_reduce_sum_(v)
             self.global_mse_sums = v[6:12].float()
             buf = _pinned("report64", self._NVEC, torch.float64, device)
@@ -257,7 +302,7 @@ class LossReport:
         """Block until the copies have landed; returns a dict of host numbers (float64 / int)."""
         self._event.synchronize()
         out = {"drmsd": 0.0, "lndrmsd": 0.0, "drmsd-bb": 0.0, "lndrmsd-bb": 0.0, "rmsd": None, "n_proteins": 0,
-               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None}
+               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None, "slddt": None}
         if self.world == 1:
             B = self._B
             host = self._buf.numpy()
@@ -273,10 +318,14 @@ class LossReport:
             if has_rmsd and B:
                 out["rmsd"] = float(np.mean(host[B * 8 + 7:B * 9 + 7].astype(np.float64)))
             if self._has_lddt:
-                sc = host[B * 9 + 7:].reshape(B, 2).astype(np.float64)
+                sc = host[B * 9 + 7:B * 9 + 7 + self._n_lddt].reshape(B, 2).astype(np.float64)
                 for k, name in enumerate(("lddt", "lddt-ca")):       # mean over the proteins with a score
                     ok = np.isfinite(sc[:, k])
                     out[name] = float(sc[ok, k].mean()) if ok.any() else float("nan")
+            if self._has_slddt:                                      # mean over the proteins with a score
+                sl = host[B * 9 + 7 + self._n_lddt:].astype(np.float64)
+                ok = np.isfinite(sl)
+                out["slddt"] = float(sl[ok].mean()) if ok.any() else float("nan")
         else:
             v = self._buf.numpy().copy()
             n = max(v[4], 1.0)
@@ -288,6 +337,8 @@ class LossReport:
                 out["rmsd"] = v[5] / v[17]
             out["lddt"] = v[19] / v[21] if v[21] > 0 else float("nan")
             out["lddt-ca"] = v[20] / v[22] if v[22] > 0 else float("nan")
+            if v[24] > 0 or self._has_slddt:
+                out["slddt"] = v[23] / v[24] if v[24] > 0 else float("nan")
         return out
 
 

@@ -117,17 +117,30 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     `args.eval_lddt` (no counterpart in the reference): in `eval_mode` the dictionary gains `lddt-full` and `lddt-ca`, the mean
     lDDT (eval_metrics.lddt_batch, on the coordinates built for the dRMSD and `rmsd-full`) over the proteins of the global batch
     that have a score.  Without the flag, and in every training step, nothing is computed and the keys are absent.
+
+    `-l slddt` (no counterpart in the reference): the structure is trained on the smooth lDDT loss of csrc/slddt.hip
+    (`--slddt_cutoff`, `--slddt_temperature`; definition in include/ptamd.h).  The injected gradient is d(sum_i slddt_i), the SUM
+    over proteins like every other structural loss here; `loss` and the new key `slddt-full` are the mean of the per-protein
+    losses over the proteins of the GLOBAL batch that have one.  The ten reference keys keep their meaning: the dRMSD statistics
+    are taken forward-only on the coordinates already built.  In `eval_mode` the loss is computed forward-only on the coordinates
+    evaluation has built.  Under any other `-l` nothing is computed and the key is absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
-    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined"] or eval_mode
+    slddt = (float(getattr(args, "slddt_cutoff", 15.0)), float(getattr(args, "slddt_temperature", 1.0))) if args.loss == "slddt" else None
+    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined", "slddt"] or eval_mode
     backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
+    if slddt is not None and backbone:
+        raise ValueError(SLDDT_BACKBONE_MESSAGE)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
-    sums = stats = grad = status = rmsd = lddt = None
+    sums = stats = grad = status = rmsd = lddt = sl = None
     if not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
-            if backbone and not eval_mode:
+            if slddt is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the smooth lDDT
+                stats, grad, status, crd, sl = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
+                                                          slddt=slddt)
+            elif backbone and not eval_mode:
                 stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
                 crd = None
             else:
@@ -146,7 +159,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
                 from .eval_metrics import lddt_batch
                 lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
-    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt)
+    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt, slddt=sl)
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -170,6 +183,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             loss = d_bb_ln_loss if backbone else ln_d_loss
         elif args.loss == "drmsd":
             loss = d_bb_loss if backbone else d_loss
+        elif args.loss == "slddt":
+            loss = np.float64(host["slddt"] if host["slddt"] is not None else float("nan"))
         elif args.loss == "combined":
             # (a training step under the flag: ln_d_loss IS the backbone value; only evaluation has two different numbers)
             loss = combine_drmsd_mse(d_bb_ln_loss, m_loss_full, w=args.combined_drmsd_weight, log=False) \
@@ -182,6 +197,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     out = {"loss": loss, "drmsd-full": d_loss, "lndrmsd-full": ln_d_loss, "drmsd-bb": d_bb_loss,
            "lndrmsd-bb": d_bb_ln_loss, "combined-full": c_loss, "mse-full": m_loss_full, "mse-bb": m_loss_bb,
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
+    if slddt is not None:
+        out["slddt-full"] = loss
     if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
         nan = float("nan")
         out["lddt-full"] = np.float64(host["lddt"] if host["lddt"] is not None else nan)
@@ -465,11 +482,34 @@ def determine_largest_batch_size(args, data, device, angle_means, fraction_to_ke
     return max_batch_size
 
 
+SLDDT_BACKBONE_MESSAGE = ("-l slddt is an all-atom loss: it cannot be combined with --backbone_loss "
+                          "(a backbone or C-alpha smooth lDDT does not exist here)")
+
+
+class _Parser(argparse.ArgumentParser):
+    """Refuses, at argument parsing, the combinations of flags that no code path serves."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.loss == "slddt" and a.backbone_loss:
+            self.error(SLDDT_BACKBONE_MESSAGE)
+        if a.loss == "slddt" and not (a.slddt_cutoff > 0 and np.isfinite(a.slddt_cutoff)
+                                      and a.slddt_temperature > 0 and np.isfinite(a.slddt_temperature)):
+            self.error("--slddt_cutoff and --slddt_temperature must be finite and positive")
+        return a
+
+
+def early_stopping_target(args):
+    """(es_mode, es_metric) of train.py:567: `-esm <train|test|valid-NN>-<loss name>`, by default the training loss of the run.
+    (Loss names carry no hyphen - `slddt` - because of this split.)"""
+    return tuple((args.early_stopping_metric or f"train-{args.loss}").rsplit("-", 1))
+
+
 def create_parser():
     """The reference's argument parser (train.py:396-529), flag for flag."""
     def my_bool(s):
         return s != 'False'
-    parser = argparse.ArgumentParser()
+    parser = _Parser()
 
     required = parser.add_argument_group("Required Args")
     required.add_argument('--data', help="Path to training data.", default="../data/proteinnet/casp12_200123_30.pt")
@@ -482,7 +522,8 @@ def create_parser():
     training.add_argument('-es', '--early_stopping', type=int, default=20)
     training.add_argument('-nws', '--n_warmup_steps', type=int, default=10_000)
     training.add_argument('-cg', '--clip', type=float, default=1)
-    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined"], default="combined")
+    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", "slddt"], default="combined",
+                          help="slddt (not in the reference): the smooth lDDT loss of AlphaFold 3 over all atoms")
     training.add_argument('--train_only', action='store_true')
     training.add_argument('--lr_scheduling', type=str, choices=['noam', 'plateau'], default='plateau')
     training.add_argument('--patience', type=int, default=10)
@@ -545,6 +586,10 @@ def create_parser():
     new = parser.add_argument_group("MI355X path additions (not in the reference)")
     new.add_argument("--max_seq_len", type=int, default=MAX_SEQ_LEN,
                      help="Positional table size / truncation length (the reference hard-wires 500).")
+    new.add_argument("--slddt_cutoff", type=float, default=15.0,
+                     help="-l slddt: inclusion radius of the smooth lDDT loss in the TRUE structure, in Angstrom.")
+    new.add_argument("--slddt_temperature", type=float, default=1.0,
+                     help="-l slddt: temperature of the four sigmoids (1 = AlphaFold 3; smaller approaches the hard lDDT).")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
@@ -564,7 +609,7 @@ def main():
         sys.exit("protein_transformer_amd runs on the MI355X only; use the reference itself for --no_cuda runs.")
     assert args.name is None or "_" not in args.name, "Please do not use underscores in experiment names."   # :577
     args.cuda = True
-    args.es_mode, args.es_metric = (args.early_stopping_metric or f"train-{args.loss}").rsplit("-", 1)
+    args.es_mode, args.es_metric = early_stopping_target(args)
     args.add_sos_eos = args.model == "enc-dec"
     args.bins = "auto" if args.bins == -1 else args.bins
     if "conv-enc" in args.model:
