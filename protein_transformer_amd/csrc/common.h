@@ -45,6 +45,11 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // ---- counter-based random words for dropout.  Masks are regenerated in the backward pass instead of stored, so the
 // generator sits in GEMM epilogues and attention inner loops: integer multiplies run at a quarter of the VALU rate on

@@ -11,10 +11,9 @@
 // slot 1, paired with C-alphas only); score = (p0.5 + p1 + p2 + p4) / (4 total), NaN without an included pair.
 //
 // Three launches per batch behind the zero fill of `counts`:
-//   compact   the present atoms of each protein, in slot order, into the caller's workspace: one 32-byte record per atom
-//             (predicted xyz, true xyz, residue code - two 16-byte loads per lane on the way to a register or to LDS, where
-//             seven separate planes would be seven 4-byte ones), and the bounding box of the true coordinates of every tile of
-//             64 compacted atoms.  A compaction of its own: csrc/drmsd.hip packs the backbone first and is left alone.
+//   compact   the present atoms of each protein, in slot order, into the caller's workspace, and the bounding box of the true
+//             coordinates of every tile of 64 of them: csrc/atom_tiles.h, shared with csrc/slddt.hip.  This file's record
+//             marks the C-alphas.  (csrc/drmsd.hip packs differently: the backbone first, for its backbone-only loss.)
 //   sweep     all ORDERED pairs (the counts belong to the row atom's residue: nothing flows to the column side, so no column
 //             partials and no triangle).  A wavefront owns a row tile of 64 atoms, one per lane, in registers; it walks a chunk
 //             of column tiles, skips those whose true bounding box lies farther than the cutoff from its own (no pair of such
@@ -25,127 +24,30 @@
 //             wavefront reduction over the lanes of one residue, one integer atomicAdd per (wavefront, residue, counter):
 //             the result does not depend on scheduling.  No fp64, no float atomics.
 //   finalize  counts -> per-residue and per-protein scores (64-bit sums over the residues).
-#include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "atom_tiles.h"
 
 namespace {
 
-constexpr int TS = 64;            // atoms per tile = lanes of a wavefront
+using namespace atom_tiles;
+
 constexpr int STRIP_TILES = 4;    // row tiles (wavefronts) per workgroup of the sweep
 constexpr int CHUNK_TILES = 32;   // column tiles per work item (<= 64: a wavefront keeps its live tiles as one ballot mask)
-constexpr int COMPACT_THREADS = 1024, FIN_THREADS = 256;
+constexpr int FIN_THREADS = 256;
 constexpr int NSET = 2, NCNT = 5;
 constexpr int CA_SLOT = 1;
 // a row or column lane behind the protein's last atom sits here in the TRUE structure (rows at +FAR, columns at -FAR): every
 // distance to it is ~1e19, finite, and fails `dt < cutoff` - no test per pair
 constexpr float FAR = 3.0e18f;
 
-// a compacted atom as the sweep reads it from LDS: two ds_read_b128 broadcasts; code = residue << 1 | (slot == C-alpha)
-struct __attribute__((aligned(32))) Atom8 {
-  float px, py, pz, tx, ty, tz;
-  int code, pad;
+// stage 1, atom_tiles::compact_kernel: the sweep reads a compacted atom from LDS as two ds_read_b128 broadcasts;
+// code = residue << 1 | (slot == C-alpha), the prediction as it came
+struct CaRecord {
+  static __device__ __forceinline__ Atom8 make(float px, float py, float pz, float tx, float ty, float tz, int res, int slot) {
+    return Atom8{px, py, pz, tx, ty, tz, (res << 1) | (slot - res * PTAMD_NUM_SLOTS == CA_SLOT), 0};
+  }
 };
-struct __attribute__((aligned(32))) Box8 {   // bounding box of the true coordinates of a tile of compacted atoms
-  float lox, loy, loz, hix, hiy, hiz, r0, r1;
-};
-
-struct Layout {
-  size_t atoms, boxes, natoms, total;
-  int nstride, tiles;   // compacted atoms per protein (a whole number of tiles), tiles per protein
-};
-inline Layout layout(int B, int L) {
-  Layout l;
-  l.tiles = (L * PTAMD_NUM_SLOTS + TS - 1) / TS;
-  l.nstride = l.tiles * TS;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  l.atoms = take((size_t)B * l.nstride * sizeof(Atom8));
-  l.boxes = take((size_t)B * l.tiles * sizeof(Box8));
-  l.natoms = take((size_t)B * sizeof(int));
-  l.total = off;
-  return l;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// ---- stage 1: compaction.  One workgroup per protein; each of its 16 wavefronts owns a contiguous share of the atom slots and
-// walks it 64 slots at a time (position of a present atom = atoms in the shares before + running count + rank among the lanes
-// before it), first counting, then writing: slot order is kept, so the atoms of a residue are neighbours.  Then, behind a
-// barrier, the bounding boxes of the tiles just written.
-__global__ __launch_bounds__(COMPACT_THREADS) void lddt_compact_kernel(const float *__restrict__ pred,
-                                                                       const float *__restrict__ truth,
-                                                                       const int64_t *__restrict__ seq, int L, int nstride,
-                                                                       int tiles, Atom8 *atoms, Box8 *boxes,
-                                                                       int *__restrict__ natoms) {
-  constexpr int NWAVE = COMPACT_THREADS / 64;
-  __shared__ int s_cnt[NWAVE];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nslot = L * PTAMD_NUM_SLOTS;
-  pred += (size_t)b * nslot * 3;
-  truth += (size_t)b * nslot * 3;
-  seq += (size_t)b * L;
-  atoms += (size_t)b * nstride;
-  boxes += (size_t)b * tiles;
-  const int per = ((nslot + NWAVE - 1) / NWAVE + 63) / 64 * 64;   // slots of a wavefront: whole rows of 64
-  const int s0 = min(w * per, nslot), s1 = min(s0 + per, nslot);
-  auto present = [&](int s, float &tx, float &ty, float &tz) __attribute__((always_inline)) {
-    tx = ty = tz = 0.f;
-    if (s >= s1 || seq[s / PTAMD_NUM_SLOTS] == PTAMD_PAD_ID) return false;   // batch padding carries zeros, not NaN
-    tx = truth[(size_t)s * 3]; ty = truth[(size_t)s * 3 + 1]; tz = truth[(size_t)s * 3 + 2];
-    return !(isnan(tx) || isnan(ty) || isnan(tz));
-  };
-  int cnt = 0;   // (wavefront-uniform)
-  for (int r = s0; r < s1; r += 64) {
-    float tx, ty, tz;
-    cnt += __popcll(__ballot(present(r + lane, tx, ty, tz)));
-  }
-  if (lane == 0) s_cnt[w] = cnt;
-  __syncthreads();
-  int pos0 = 0, n = 0;
-#pragma unroll
-  for (int t = 0; t < NWAVE; ++t) {
-    if (t < w) pos0 += s_cnt[t];
-    n += s_cnt[t];
-  }
-  for (int r = s0; r < s1; r += 64) {
-    float tx, ty, tz;
-    const int s = r + lane;
-    const bool ok = present(s, tx, ty, tz);
-    const unsigned long long m = __ballot(ok);
-    if (ok) {
-      const int pos = pos0 + __popcll(m & ((1ull << lane) - 1ull));
-      const int res = s / PTAMD_NUM_SLOTS;
-      atoms[pos] = Atom8{pred[(size_t)s * 3], pred[(size_t)s * 3 + 1], pred[(size_t)s * 3 + 2], tx, ty, tz,
-                         (res << 1) | (s - res * PTAMD_NUM_SLOTS == CA_SLOT), 0};
-    }
-    pos0 += __popcll(m);
-  }
-  if (tid == 0) natoms[b] = n;
-  __syncthreads();   // the atoms this workgroup wrote are visible to all of it
-  const float inf = __builtin_inff();
-  for (int t = w; t * TS < n; t += NWAVE) {
-    const int j = t * TS + lane;
-    const bool live = j < n;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (live) {
-      const Atom8 a = atoms[j];
-      x = a.tx; y = a.ty; z = a.tz;
-    }
-    const float lox = wave_min(live ? x : inf), loy = wave_min(live ? y : inf), loz = wave_min(live ? z : inf);
-    const float hix = wave_max(live ? x : -inf), hiy = wave_max(live ? y : -inf), hiz = wave_max(live ? z : -inf);
-    if (lane == 0) boxes[t] = Box8{lox, loy, loz, hix, hiy, hiz, 0.f, 0.f};
-  }
-}
 
 // ---- stage 2: the pair sweep.  Workgroup = 4 wavefronts = 4 consecutive row tiles against one chunk of column tiles; the
 // wavefronts do not talk to each other (each stages its column tiles in its own LDS slice: no workgroup barrier anywhere).
@@ -182,19 +84,12 @@ __global__ __launch_bounds__(TS * STRIP_TILES) void lddt_sweep_kernel(const Atom
   atoms += (size_t)b * nstride;
   boxes += (size_t)b * tiles;
 
-  // which column tiles of the chunk can hold an included pair: lane l tests tile J0 + l against this row tile's box.  The true
-  // distance of a pair is at least the gap between the two boxes; 0.1 % on the squares covers the rounding of both sides.
+  // which column tiles of the chunk can hold an included pair: lane l tests tile J0 + l against this row tile's box
   unsigned long long todo;
   {
     const Box8 me = boxes[I];
     bool near = false;
-    if (J0 + lane < J1) {
-      const Box8 c = boxes[J0 + lane];
-      const float gx = fmaxf(0.f, fmaxf(me.lox - c.hix, c.lox - me.hix));
-      const float gy = fmaxf(0.f, fmaxf(me.loy - c.hiy, c.loy - me.hiy));
-      const float gz = fmaxf(0.f, fmaxf(me.loz - c.hiz, c.loz - me.hiz));
-      near = !(gx * gx + gy * gy + gz * gz > cutoff * cutoff * 1.001f);   // (a NaN gap keeps the tile)
-    }
+    if (J0 + lane < J1) near = boxes_near(me, boxes[J0 + lane], cutoff);
     todo = __ballot(near);
   }
   if (todo == 0ull) return;
@@ -234,8 +129,7 @@ __global__ __launch_bounds__(TS * STRIP_TILES) void lddt_sweep_kernel(const Atom
         const Atom8 c = col[j];   // broadcast
         const float dxt = me.tx - c.tx, dyt = me.ty - c.ty, dzt = me.tz - c.tz;
         const float dxp = me.px - c.px, dyp = me.py - c.py, dzp = me.pz - c.pz;
-        const float dt = __builtin_amdgcn_sqrtf(fmaf(dzt, dzt, fmaf(dyt, dyt, dxt * dxt)));
-        const float dp = __builtin_amdgcn_sqrtf(fmaf(dzp, dzp, fmaf(dyp, dyp, dxp * dxp)));
+        const float dt = true_dist(dxt, dyt, dzt), dp = true_dist(dxp, dyp, dzp);
         const bool incl = dt < cutoff && (unsigned)(me.code ^ c.code) > 1u;   // strict; different residues
         const unsigned E = (__float_as_uint(dp - dt) >> 23) & 0xffu;
         const unsigned h = min(max(E, 125u), 129u) - 125u;
@@ -323,17 +217,17 @@ __global__ __launch_bounds__(FIN_THREADS) void lddt_finalize_kernel(const int32_
 extern "C" {
 
 size_t ptamd_lddt_workspace_bytes(int B, int L) {
-  if (B <= 0 || L <= 0 || L > INT_MAX / (2 * PTAMD_NUM_SLOTS)) return 0;
-  return layout(B, L).total;
+  if (!tile_shape_ok(B, L)) return 0;
+  return TileLayout(B, L).end;   // the tiles are all of it
 }
 
 int ptamd_lddt(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff, int32_t *counts,
                float *per_res, float *score, void *workspace, size_t workspace_bytes, void *stream) {
-  if (B <= 0 || L <= 0 || L > INT_MAX / (2 * PTAMD_NUM_SLOTS)) return PTAMD_ERR_BAD_SHAPE;   // (slot indices and residue codes are ints)
+  if (!tile_shape_ok(B, L)) return PTAMD_ERR_BAD_SHAPE;
   if (!pred_crd || !true_crd || !seq || !counts || !per_res || !score) return PTAMD_ERR_BAD_SHAPE;
   if (!(cutoff > 0.f) || !isfinite(cutoff)) return PTAMD_ERR_BAD_SHAPE;
-  const Layout l = layout(B, L);
-  if (!workspace || workspace_bytes < l.total) return PTAMD_ERR_WORKSPACE;
+  const TileLayout l(B, L);
+  if (!workspace || workspace_bytes < l.end) return PTAMD_ERR_WORKSPACE;
   if (!pt_aligned16(workspace)) return PTAMD_ERR_ALIGN;
   char *ws = static_cast<char *>(workspace);
   Atom8 *atoms = reinterpret_cast<Atom8 *>(ws + l.atoms);
@@ -341,7 +235,7 @@ int ptamd_lddt(const float *pred_crd, const float *true_crd, const int64_t *seq,
   int *natoms = reinterpret_cast<int *>(ws + l.natoms);
   hipStream_t st = (hipStream_t)stream;
   PT_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)B * L * NSET * NCNT * sizeof(int32_t), st));   // the sweep only adds
-  hipLaunchKernelGGL(lddt_compact_kernel, dim3(B), dim3(COMPACT_THREADS), 0, st, pred_crd, true_crd, seq, L, l.nstride, l.tiles,
+  hipLaunchKernelGGL(compact_kernel<CaRecord>, dim3(B), dim3(COMPACT_THREADS), 0, st, pred_crd, true_crd, seq, L, l.nstride, l.tiles,
                      atoms, boxes, natoms);
   int rc = pt_check_launch();
   if (rc) return rc;

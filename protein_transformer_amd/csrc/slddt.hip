@@ -7,11 +7,11 @@
 // argument of the logistics (tau = 1 is AlphaFold 3's loss, tau -> 0 the hard lDDT).  Definition: include/ptamd.h.
 //
 // Three launches per batch behind the zero fill of `dcrd`:
-//   compact   the present atoms of each protein, in slot order, into the workspace: one 32-byte record per atom (predicted xyz,
-//             true xyz, residue code, slot) and the bounding box of the TRUE coordinates of every tile of 64 compacted atoms -
-//             the compaction of csrc/lddt.hip with two more fields (that file is left alone: ptamd_lddt keeps its bits).  A
-//             predicted coordinate that is not finite (or beyond 1e18: its squared differences would not be) is replaced by 0
-//             and the atom marked: its pairs are counted, score 0 and carry no gradient - nothing non-finite enters the sweep.
+//   compact   the present atoms of each protein, in slot order, into the workspace, and the bounding box of the TRUE
+//             coordinates of every tile of 64 of them: csrc/atom_tiles.h, shared with csrc/lddt.hip.  This file's record keeps
+//             the atom's slot, and a predicted coordinate that is not finite (or beyond 1e18: its squared differences would
+//             not be) is replaced by 0 and the atom marked: its pairs are counted, score 0 and carry no gradient - nothing
+//             non-finite enters the sweep.  (csrc/drmsd.hip packs differently: the backbone first, for its backbone-only loss.)
 //   sweep     the UPPER TRIANGLE of tile pairs, every unordered pair of atoms once.  A work item is one wavefront: a STRIP of 4
 //             row tiles (one atom per lane and tile, in registers) against a CHUNK of 8 column tiles.  Per column tile J the
 //             wavefront stages the tile in LDS and visits the row tiles I <= J of its strip whose true bounding box lies within
@@ -32,25 +32,26 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "atom_tiles.h"
 
 namespace {
 
-constexpr int TS = 64;            // atoms per tile = lanes of a wavefront
+using namespace atom_tiles;
+
 constexpr int STRIP_TILES = 4;    // row tiles of a work item
 constexpr int CHUNK_TILES = 8;    // column tiles of a work item (<= 64: a lane tests one column tile's box)
 constexpr int SUB = 16, CF_LD = SUB + 1;   // the coefficient tile is kept for 16 columns at a time: 4.3 KB
-constexpr int COMPACT_THREADS = 1024, FIN_THREADS = 256;
+constexpr int FIN_THREADS = 256;
 constexpr int NTHR = 4;           // thresholds 0.5, 1, 2, 4
 constexpr float PRED_MAX = 1.0e18f;
 
-// a compacted atom: two 16-byte loads; code = residue << 1 | (predicted coordinate unusable), -1 behind the last atom
-struct __attribute__((aligned(32))) Atom8 {
-  float px, py, pz, tx, ty, tz;
-  int code, slot;
-};
-struct __attribute__((aligned(32))) Box8 {   // bounding box of the true coordinates of a tile of compacted atoms
-  float lox, loy, loz, hix, hiy, hiz, r0, r1;
+// stage 1, atom_tiles::compact_kernel: code = residue << 1 | (predicted coordinate unusable), -1 behind the last atom; aux = slot
+struct SlotRecord {
+  static __device__ __forceinline__ Atom8 make(float px, float py, float pz, float tx, float ty, float tz, int res, int slot) {
+    const bool bad = !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
+    if (bad) px = py = pz = 0.f;
+    return Atom8{px, py, pz, tx, ty, tz, (res << 1) | (int)bad, slot};
+  }
 };
 struct __attribute__((aligned(16))) Item {   // what one work item of the sweep leaves for the finalize kernel
   double eps;        // sum over its scored pairs of the four logistics
@@ -65,119 +66,24 @@ struct Consts {
 };
 
 struct Layout {
-  size_t atoms, boxes, natoms, rowpart, colpart, kept, items, total;
-  int nstride, tiles, strips, chunks;
+  TileLayout t;
+  size_t rowpart, colpart, kept, items, total;
+  int strips, chunks;
+  Layout(int B, int L) : t(B, L) {
+    strips = (t.tiles + STRIP_TILES - 1) / STRIP_TILES;
+    chunks = (t.tiles + CHUNK_TILES - 1) / CHUNK_TILES;
+    total = t.end;
+    rowpart = take(total, (size_t)B * t.tiles * chunks * TS * sizeof(float4));   // [b][row tile][chunk][lane]
+    colpart = take(total, (size_t)B * strips * t.tiles * TS * sizeof(float4));   // [b][strip][column tile][lane]
+    kept = take(total, (size_t)B * strips * t.tiles * sizeof(int));              // [b][strip][column tile]
+    items = take(total, (size_t)B * strips * chunks * sizeof(Item));             // [b][strip][chunk]
+  }
 };
-inline Layout layout(int B, int L) {
-  Layout l;
-  l.tiles = (L * PTAMD_NUM_SLOTS + TS - 1) / TS;
-  l.nstride = l.tiles * TS;
-  l.strips = (l.tiles + STRIP_TILES - 1) / STRIP_TILES;
-  l.chunks = (l.tiles + CHUNK_TILES - 1) / CHUNK_TILES;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  l.atoms = take((size_t)B * l.nstride * sizeof(Atom8));
-  l.boxes = take((size_t)B * l.tiles * sizeof(Box8));
-  l.natoms = take((size_t)B * sizeof(int));
-  l.rowpart = take((size_t)B * l.tiles * l.chunks * TS * sizeof(float4));    // [b][row tile][chunk][lane]
-  l.colpart = take((size_t)B * l.strips * l.tiles * TS * sizeof(float4));    // [b][strip][column tile][lane]
-  l.kept = take((size_t)B * l.strips * l.tiles * sizeof(int));               // [b][strip][column tile]
-  l.items = take((size_t)B * l.strips * l.chunks * sizeof(Item));            // [b][strip][chunk]
-  l.total = off;
-  return l;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// ---- stage 1: compaction (csrc/lddt.hip: one workgroup per protein, each wavefront a contiguous share of the slots, slot order
-// kept), then the bounding boxes of the tiles just written
-__global__ __launch_bounds__(COMPACT_THREADS) void slddt_compact_kernel(const float *__restrict__ pred,
-                                                                        const float *__restrict__ truth,
-                                                                        const int64_t *__restrict__ seq, int L, int nstride,
-                                                                        int tiles, Atom8 *atoms, Box8 *boxes,
-                                                                        int *__restrict__ natoms) {
-  constexpr int NWAVE = COMPACT_THREADS / 64;
-  __shared__ int s_cnt[NWAVE];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nslot = L * PTAMD_NUM_SLOTS;
-  pred += (size_t)b * nslot * 3;
-  truth += (size_t)b * nslot * 3;
-  seq += (size_t)b * L;
-  atoms += (size_t)b * nstride;
-  boxes += (size_t)b * tiles;
-  const int per = ((nslot + NWAVE - 1) / NWAVE + 63) / 64 * 64;   // slots of a wavefront: whole rows of 64
-  const int s0 = min(w * per, nslot), s1 = min(s0 + per, nslot);
-  auto present = [&](int s, float &tx, float &ty, float &tz) __attribute__((always_inline)) {
-    tx = ty = tz = 0.f;
-    if (s >= s1 || seq[s / PTAMD_NUM_SLOTS] == PTAMD_PAD_ID) return false;   // batch padding carries zeros, not NaN
-    tx = truth[(size_t)s * 3]; ty = truth[(size_t)s * 3 + 1]; tz = truth[(size_t)s * 3 + 2];
-    return !(isnan(tx) || isnan(ty) || isnan(tz));
-  };
-  int cnt = 0;   // (wavefront-uniform)
-  for (int r = s0; r < s1; r += 64) {
-    float tx, ty, tz;
-    cnt += __popcll(__ballot(present(r + lane, tx, ty, tz)));
-  }
-  if (lane == 0) s_cnt[w] = cnt;
-  __syncthreads();
-  int pos0 = 0, n = 0;
-#pragma unroll
-  for (int t = 0; t < NWAVE; ++t) {
-    if (t < w) pos0 += s_cnt[t];
-    n += s_cnt[t];
-  }
-  for (int r = s0; r < s1; r += 64) {
-    float tx, ty, tz;
-    const int s = r + lane;
-    const bool ok = present(s, tx, ty, tz);
-    const unsigned long long m = __ballot(ok);
-    if (ok) {
-      const int pos = pos0 + __popcll(m & ((1ull << lane) - 1ull));
-      float px = pred[(size_t)s * 3], py = pred[(size_t)s * 3 + 1], pz = pred[(size_t)s * 3 + 2];
-      const bool bad = !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
-      if (bad) px = py = pz = 0.f;
-      atoms[pos] = Atom8{px, py, pz, tx, ty, tz, ((s / PTAMD_NUM_SLOTS) << 1) | (int)bad, s};
-    }
-    pos0 += __popcll(m);
-  }
-  if (tid == 0) natoms[b] = n;
-  __syncthreads();   // the atoms this workgroup wrote are visible to all of it
-  const float inf = __builtin_inff();
-  for (int t = w; t * TS < n; t += NWAVE) {
-    const int j = t * TS + lane;
-    const bool live = j < n;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (live) {
-      const Atom8 a = atoms[j];
-      x = a.tx; y = a.ty; z = a.tz;
-    }
-    const float lox = wave_min(live ? x : inf), loy = wave_min(live ? y : inf), loz = wave_min(live ? z : inf);
-    const float hix = wave_max(live ? x : -inf), hiy = wave_max(live ? y : -inf), hiz = wave_max(live ? z : -inf);
-    if (lane == 0) boxes[t] = Box8{lox, loy, loz, hix, hiy, hiz, 0.f, 0.f};
-  }
-}
-
-// can a pair of atoms of two tiles be included?  Its true distance is at least the gap between the boxes; 0.1 % on the squares
-// covers the rounding of both sides (a NaN gap keeps the tile)
-__device__ __forceinline__ bool boxes_near(const Box8 &a, const Box8 &c, float cutoff) {
-  const float gx = fmaxf(0.f, fmaxf(a.lox - c.hix, c.lox - a.hix));
-  const float gy = fmaxf(0.f, fmaxf(a.loy - c.hiy, c.loy - a.hiy));
-  const float gz = fmaxf(0.f, fmaxf(a.loz - c.hiz, c.loz - a.hiz));
-  return !(gx * gx + gy * gy + gz * gz > cutoff * cutoff * 1.001f);
-}
 
 // ---- stage 2: the pair sweep.  grid (strips * chunks, B), one wavefront per workgroup = one work item.
-// Per pair (phase 1), with q the sums of squares: 6 subtractions, 6 multiply-adds, v_sqrt_f32 of both (the true distance and the
-// inclusion test are bit for bit those of lddt_sweep_kernel; the predicted one is the same function of its q, so a prediction
-// equal to the truth has delta == 0 exactly), v_rsq_f32 for 1 / dp (gradient only), one v_exp_f32 and four v_rcp_f32 for the
+// Per pair (phase 1), with q the sums of squares: 6 subtractions, 6 multiply-adds, v_sqrt_f32 of both (the true distance is
+// atom_tiles' true_dist, as in lddt_sweep_kernel; the predicted one is the same function of its q, so a prediction equal to the
+// truth has delta == 0 exactly), v_rsq_f32 for 1 / dp (gradient only), one v_exp_f32 and four v_rcp_f32 for the
 // logistics.  The clamp of csrc/drmsd.hip under the root is the 1e-30 added to the predicted squares - to their rounded SUM, not
 // as the addend of the first multiply-add: there it breaks a rounding tie of dx^2 (differences of stored coordinates have few
 // significant bits, so exact ties do occur) and leaves dp one ulp above dt for a prediction equal to the truth.
@@ -252,7 +158,7 @@ __global__ __launch_bounds__(TS) void slddt_sweep_kernel(const Atom8 *__restrict
           const float dxt = a.tx - c.tx, dyt = a.ty - c.ty, dzt = a.tz - c.tz;
           const float dxp = a.px - c.px, dyp = a.py - c.py, dzp = a.pz - c.pz;
           const float qp = fmaf(dzp, dzp, fmaf(dyp, dyp, dxp * dxp)) + 1e-30f;   // (the sum itself above 1e-22)
-          const float dt = __builtin_amdgcn_sqrtf(fmaf(dzt, dzt, fmaf(dyt, dyt, dxt * dxt)));
+          const float dt = true_dist(dxt, dyt, dzt);
           const float dp = __builtin_amdgcn_sqrtf(qp);
           // strict; different residues; a column behind the last atom has code -1 (and a dead row is excluded by a_live)
           const bool incl = dt < k.cutoff && (unsigned)(a.code ^ c.code) > 1u && c.code >= 0 && a_live && (!diag || lane < j);
@@ -388,38 +294,36 @@ __global__ __launch_bounds__(FIN_THREADS) void slddt_finalize_kernel(const Atom8
     cy += fmaf(a.py, cp.x, -cp.z);
     cz += fmaf(a.pz, cp.x, -cp.w);
   }
-  float *out = dcrd + ((size_t)b * nslot + a.slot) * 3;
+  float *out = dcrd + ((size_t)b * nslot + a.aux) * 3;
   const bool bad = a.code & 1;   // (its coefficients are all zero: written as a plain 0)
   out[0] = bad ? 0.f : scale * (rx + cx);
   out[1] = bad ? 0.f : scale * (ry + cy);
   out[2] = bad ? 0.f : scale * (rz + cz);
 }
 
-inline bool shape_ok(int B, int L) { return B > 0 && L > 0 && L <= INT_MAX / (2 * PTAMD_NUM_SLOTS); }   // the bound of ptamd_lddt
-
 }  // namespace
 
 extern "C" {
 
 size_t ptamd_slddt_workspace_bytes(int B, int L) {
-  if (!shape_ok(B, L)) return 0;
-  return layout(B, L).total;
+  if (!tile_shape_ok(B, L)) return 0;
+  return Layout(B, L).total;
 }
 
 int ptamd_slddt_fwd_bwd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff,
                         float temperature, float *stats, int64_t *npairs, float *dcrd, void *workspace, size_t workspace_bytes,
                         void *stream) {
-  if (!shape_ok(B, L)) return PTAMD_ERR_BAD_SHAPE;
+  if (!tile_shape_ok(B, L)) return PTAMD_ERR_BAD_SHAPE;
   if (!pred_crd || !true_crd || !seq || !stats || !npairs) return PTAMD_ERR_BAD_SHAPE;
   if (!(cutoff > 0.f) || !isfinite(cutoff) || !(temperature > 0.f) || !isfinite(temperature)) return PTAMD_ERR_BAD_SHAPE;
-  const Layout l = layout(B, L);
+  const Layout l(B, L);
   if (!workspace || workspace_bytes < l.total) return PTAMD_ERR_WORKSPACE;
   if (!pt_aligned16(workspace)) return PTAMD_ERR_ALIGN;
   if ((size_t)l.strips * l.chunks > (size_t)INT_MAX) return PTAMD_ERR_BAD_SHAPE;   // (a grid dimension; its workspace is beyond any device)
   char *ws = static_cast<char *>(workspace);
-  Atom8 *atoms = reinterpret_cast<Atom8 *>(ws + l.atoms);
-  Box8 *boxes = reinterpret_cast<Box8 *>(ws + l.boxes);
-  int *natoms = reinterpret_cast<int *>(ws + l.natoms);
+  Atom8 *atoms = reinterpret_cast<Atom8 *>(ws + l.t.atoms);
+  Box8 *boxes = reinterpret_cast<Box8 *>(ws + l.t.boxes);
+  int *natoms = reinterpret_cast<int *>(ws + l.t.natoms);
   float4 *rowpart = reinterpret_cast<float4 *>(ws + l.rowpart), *colpart = reinterpret_cast<float4 *>(ws + l.colpart);
   int *kept = reinterpret_cast<int *>(ws + l.kept);
   Item *items = reinterpret_cast<Item *>(ws + l.items);
@@ -438,17 +342,17 @@ int ptamd_slddt_fwd_bwd(const float *pred_crd, const float *true_crd, const int6
   hipStream_t st = (hipStream_t)stream;
   const int nslot = L * PTAMD_NUM_SLOTS;
   if (dcrd) PT_HIP_TRY(hipMemsetAsync(dcrd, 0, (size_t)B * nslot * 3 * sizeof(float), st));   // slots of absent atoms stay 0
-  hipLaunchKernelGGL(slddt_compact_kernel, dim3(B), dim3(COMPACT_THREADS), 0, st, pred_crd, true_crd, seq, L, l.nstride, l.tiles,
+  hipLaunchKernelGGL(compact_kernel<SlotRecord>, dim3(B), dim3(COMPACT_THREADS), 0, st, pred_crd, true_crd, seq, L, l.t.nstride, l.t.tiles,
                      atoms, boxes, natoms);
   int rc = pt_check_launch();
   if (rc) return rc;
   auto sweep = dcrd ? slddt_sweep_kernel<true> : slddt_sweep_kernel<false>;
-  hipLaunchKernelGGL(sweep, dim3((unsigned)(l.strips * l.chunks), B), dim3(TS), 0, st, atoms, boxes, natoms, l.nstride, l.tiles,
+  hipLaunchKernelGGL(sweep, dim3((unsigned)(l.strips * l.chunks), B), dim3(TS), 0, st, atoms, boxes, natoms, l.t.nstride, l.t.tiles,
                      l.strips, l.chunks, k, rowpart, colpart, kept, items);
   rc = pt_check_launch();
   if (rc) return rc;
-  hipLaunchKernelGGL(slddt_finalize_kernel, dim3(dcrd ? (unsigned)((l.nstride + FIN_THREADS - 1) / FIN_THREADS) : 1u, B),
-                     dim3(FIN_THREADS), 0, st, atoms, natoms, rowpart, colpart, kept, items, l.nstride, l.tiles, l.strips,
+  hipLaunchKernelGGL(slddt_finalize_kernel, dim3(dcrd ? (unsigned)((l.t.nstride + FIN_THREADS - 1) / FIN_THREADS) : 1u, B),
+                     dim3(FIN_THREADS), 0, st, atoms, natoms, rowpart, colpart, kept, items, l.t.nstride, l.t.tiles, l.strips,
                      l.chunks, gscale, stats, reinterpret_cast<long long *>(npairs), dcrd, nslot);
   return pt_check_launch();
 }

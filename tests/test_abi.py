@@ -56,6 +56,13 @@ def test_host_only_entry_points(built_lib):
     assert lib.ptamd_gemm_workspace_bytes(512, 512, 1) == (512 + 512) * 4    # row scales of the f16x2 arithmetic
     assert lib.ptamd_gemm_workspace_bytes(512, 512, 8) == (8 * 512 * 512 + 8 * 16 * 512) * 4 + (512 + 512) * 4   # + C / column-sum slabs
     assert lib.ptamd_gemm_workspace_bytes(510, 30, 1) == (512 + 32) * 4
+    # lDDT and the smooth lDDT share the head of their workspace (csrc/atom_tiles.h): sizes pinned, every piece rounded to 256 B
+    for (B, L), lddt, slddt in [((1, 1), 2560, 5120), ((2, 10), 12800, 25600), ((3, 37), 56576, 195840)]:
+        assert (lib.ptamd_lddt_workspace_bytes(B, L), lib.ptamd_slddt_workspace_bytes(B, L)) == (lddt, slddt), (B, L)
+    l_max = (2 ** 31 - 1) // 28                                      # slot indices and residue codes are ints
+    for ws in (lib.ptamd_lddt_workspace_bytes, lib.ptamd_slddt_workspace_bytes):
+        assert ws(0, 8) == 0 and ws(2, 0) == 0 and ws(1, l_max + 1) == 0
+        assert ws(1, l_max) > 0                                      # only a size: nothing is allocated
     # argument validation happens on the host, before any launch
     assert lib.ptamd_nerf_fwd(None, None, 0, 5, None, None, None) == -1          # PTAMD_ERR_BAD_SHAPE
     assert lib.ptamd_nerf_fwd(None, None, 2, 5000, None, None, None) == -2       # PTAMD_ERR_TOO_LONG
