@@ -97,10 +97,7 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_fwd_kernel(const floa
   load_row_frag<DK>(base, D3, q, q_ok, lh, qf);
 
   f32x16 o[NDT];
-#pragma unroll
-  for (int t = 0; t < NDT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  acc_zero(o);
   float m_run = -INFINITY, l_run = 0.f;
 
   Stage<DK, KT> stK, stV;
@@ -191,15 +188,7 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_fwd_kernel(const floa
   const float inv = (p_drop > 0.f ? dk_.ks : 1.f) / l_tot;  // softmax normalisation and the dropout scale in one factor
   if (q_ok) {
     float *op = out + (size_t)(b * L + q) * D + h * DK;
-#pragma unroll
-    for (int t = 0; t < NDT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        if (d < DK)
-          *reinterpret_cast<float4 *>(op + d) =
-              make_float4(o[t][4 * g] * inv, o[t][4 * g + 1] * inv, o[t][4 * g + 2] * inv, o[t][4 * g + 3] * inv);
-      }
+    acc_store_rows<DK>(op, o, lh, inv);
     if (lh == 0) lse[((size_t)b * H + h) * L + q] = m_run + logf(l_tot);
   }
 }
@@ -244,10 +233,7 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dq_kernel(const f
   }
 
   f32x16 dq[NDT];
-#pragma unroll
-  for (int t = 0; t < NDT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[t][r] = 0.f;
+  acc_zero(dq);
 
   Stage<DK, KT> stK, stV;
   const int ntiles = (L + KT - 1) / KT;
@@ -318,14 +304,7 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dq_kernel(const f
   }
   if (q_ok) {
     float *op = dqkv + (size_t)(b * L + q) * D3 + h * DK;
-#pragma unroll
-    for (int t = 0; t < NDT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        if (d < DK)
-          *reinterpret_cast<float4 *>(op + d) = make_float4(dq[t][4 * g], dq[t][4 * g + 1], dq[t][4 * g + 2], dq[t][4 * g + 3]);
-      }
+    acc_store_rows<DK>(op, dq, lh);
   }
 }
 
@@ -356,10 +335,8 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dkv_kernel(const 
   load_row_frag<DK>(base + 2 * D, D3, key, k_ok, lh, vf);
 
   f32x16 dk[NDT], dv[NDT];
-#pragma unroll
-  for (int t = 0; t < NDT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dk[t][r] = dv[t][r] = 0.f;
+  acc_zero(dk);
+  acc_zero(dv);
 
   Stage<DK, QT> stQ, stG;
   const int ntiles = (L + QT - 1) / QT;
@@ -437,16 +414,8 @@ __global__ __launch_bounds__(256, F32_WAVES<DK>) void attn_bwd_dkv_kernel(const 
   }
   if (k_ok) {
     float *okp = dqkv + (size_t)(b * L + key) * D3 + D + h * DK, *ovp = okp + D;
-#pragma unroll
-    for (int t = 0; t < NDT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        if (d < DK) {
-          *reinterpret_cast<float4 *>(okp + d) = make_float4(dk[t][4 * g], dk[t][4 * g + 1], dk[t][4 * g + 2], dk[t][4 * g + 3]);
-          *reinterpret_cast<float4 *>(ovp + d) = make_float4(dv[t][4 * g], dv[t][4 * g + 1], dv[t][4 * g + 2], dv[t][4 * g + 3]);
-        }
-      }
+    acc_store_rows<DK>(okp, dk, lh);
+    acc_store_rows<DK>(ovp, dv, lh);
   }
 }
 

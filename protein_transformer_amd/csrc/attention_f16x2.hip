@@ -396,6 +396,120 @@ constexpr int BUF = 2 * Tile2::ELEMS;  // f16 elements of one {A, B} tile buffer
 constexpr size_t ATTN_LDS = (size_t)2 * BUF * sizeof(unsigned short);
 
 // =================================================================================================== forward
+// key mask of the 32-key tile at k0 as an ADDITIVE term of the soft-max argument (0 or -inf per key), read back one float4 per
+// register quadruple: no bit extraction and no select per element
+__device__ __forceinline__ void publish_key_mask(float *__restrict__ bias, const int64_t *__restrict__ sq, int k0, int L, int tid) {
+  if (tid < TR) {
+    const int key = k0 + tid;
+    bias[tid] = (key < L && sq[key < L ? key : 0] != PTAMD_PAD_ID) ? 0.f : -INFINITY;
+  }
+}
+
+// What a wavefront carries from key tile to key tile for its 32 queries (lane = query l31; a lane half the keys of its register
+// quadruples): O^T scaled by 2^14 / v_run, and the soft-max statistics of the lane half.
+template <int NT>
+struct FwdState {
+  f32x16 o[NT];
+  float m_run, l_run;  // running maximum (log2 units), row sum of this lane half
+  float v_run;         // largest inverse V group scale so far (a power of two; wavefront-uniform)
+  __device__ __forceinline__ void init() {
+    acc_zero(o);
+    m_run = -INFINITY;
+    l_run = v_run = 0.f;
+  }
+  // the query's row of `out` and its lse; ks: the dropout scale 1 / (1 - p), or 1
+  __device__ __forceinline__ void finish(float ks, bool q_ok, int lh, float *__restrict__ out_row, float *__restrict__ lse_q) const {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    // soft-max normalisation, dropout scale and the common V scale in one factor
+    const float inv = ks * v_run * INV_TWO14 / l_tot;
+    if (q_ok) {
+      acc_store_rows<32 * NT>(out_row, o, lh, inv);
+      if (lh == 0) *lse_q = (m_run + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
+    }
+  }
+};
+
+// One 32-key tile of the forward pass: scores, on-line soft-max, dropout, O^T += V^T P^T.  The one body of both forward kernels -
+// they differ in how a tile gets into LDS, which stays with them, and hand in what depends on it:
+//   k_rows(ks, f)     row fragment ks of the K tile (d = 16 ks + 8 lh + 0..7 of key l31)
+//   v_cols(kb, t, f)  transposed fragment of the V tile: columns d = 32 t + l31 of the keys kb + ..  (Tile2::frag_cols)
+//   between()         runs behind the score products, in front of the soft-max: where a kernel that stages by hand converts and
+//                     stores the next tile
+//   export_word(w)    (export_bits) the dropout decisions of the tile, lane = key, bit = query: the kernel stores them
+// ik4: the inverse scales of the four key groups of this lane half; iva, ivb: those of the eight V groups; bias: the tile's key
+// mask (publish_key_mask), in LDS.
+template <int DK, typename KRows, typename VCols, typename Between, typename Export>
+__device__ __forceinline__ void fwd_tile_step(FwdState<DK / 32> &st, const f16x8 (&qf)[DK / 16][2], float cq, const float4 &ik4,
+                                              const float4 &iva, const float4 &ivb, const float *__restrict__ bias, int k0,
+                                              const AttnDrop &drop, uint32_t q_part, float p_drop, bool export_bits, int lh,
+                                              KRows k_rows, VCols v_cols, Between between, Export export_word) {
+  constexpr int KS = DK / 16, NT = DK / 32;
+  f32x16 s;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {  // S^T[key][q] = K Q^T (scaled operands)
+    f16x8 kf[2];
+    k_rows(ks, kf);
+    s = mfma3(kf, qf[ks], s);
+  }
+  between();
+  const float cu[4] = {cq * ik4.x, cq * ik4.y, cq * ik4.z, cq * ik4.w};
+  float mt = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float4 b4 = *reinterpret_cast<const float4 *>(bias + 8 * j + 4 * lh);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {  // (s cu is finite - a masked group of zero rows has s = cu = 0 - so the sum is -inf, not NaN)
+      s[4 * j + e] = fmaf(s[4 * j + e], cu[j], f4_at(b4, e));
+      mt = fmaxf(mt, s[4 * j + e]);
+    }
+  }
+  mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+  const float m_new = fmaxf(st.m_run, mt);
+  const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+  const float alpha = __builtin_amdgcn_exp2f(st.m_run - m_safe);
+  float ps = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    s[r] = __builtin_amdgcn_exp2f(s[r] - m_safe);
+    ps += s[r];
+  }
+  st.l_run = st.l_run * alpha + ps;
+  st.m_run = m_new;
+  // common scale of the V groups: O accumulates  sum P (iv_g / v_run) 2^14 * (V sv_g)  =  (2^14 / v_run) sum P V
+  const float vt = max8(iva, ivb);
+  float resc = alpha;
+  if (vt > st.v_run) {
+    resc *= st.v_run * inv_pow2(vt);
+    st.v_run = vt;
+  }
+  if (__builtin_amdgcn_ballot_w64(resc != 1.f)) acc_scale(st.o, resc);  // wave-uniform: after the first tiles neither maximum moves often
+  const float vn = inv_pow2(st.v_run);
+  const float4 ivh = lh ? ivb : iva;
+  const float fv[4] = {ivh.x * TWO14 * vn, ivh.y * TWO14 * vn, ivh.z * TWO14 * vn, ivh.w * TWO14 * vn};  // <= 2^14
+  if (p_drop > 0.f) {   // the 1 / (1 - p) is applied to O at the end
+    if (export_bits) {  // (uniform) the decisions also go out for the fused backward kernel: attn_dropout.h
+      export_word(attn_drop_keys_in_rows_export(drop, q_part, k0, lh, s));
+    } else {
+      attn_drop_keys_in_rows(drop, q_part, k0, lh, s);
+    }
+  }
+  // O^T[d][q] += V^T[d][key] P^T[key][q]: the accumulator rows of s are already in the k order of frag_cols
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const float x[8] = {s[8 * m], s[8 * m + 1], s[8 * m + 2], s[8 * m + 3], s[8 * m + 4], s[8 * m + 5], s[8 * m + 6], s[8 * m + 7]};
+    f16x8 pf[2];
+    split8g(x, fv[2 * m], fv[2 * m + 1], pf);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      f16x8 vf[2];
+      v_cols(16 * m, t, vf);
+      st.o[t] = mfma3(vf, pf, st.o[t]);
+    }
+  }
+}
+
 #ifndef PT_ATTN_FWD_WAVES
 #define PT_ATTN_FWD_WAVES 2   // wavefronts per SIMD the forward kernel is compiled for (4 = 128 VGPRs: 27 spilled, measured in round 4)
 #endif
@@ -428,27 +542,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
   const float iq = load_row_scaled<KS>(base, D3, min(q, L - 1), q_ok, lh, qf);
   const float cq = scale * LOG2E * iq;  // scores leave the accumulators in log2 units: exp(x) = exp2(x log2 e)
 
-  f32x16 o[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;  // running maximum in log2 units
-  float v_run = 0.f;                     // largest inverse V group scale so far (a power of two; wavefront-uniform)
+  FwdState<NT> state;
+  state.init();
 
   constexpr int TE = HALVES<DK> * TILE::ELEMS;  // f16 elements of one staged tile
   constexpr int TBUF = 2 * TE;                   // ... of one {K, V} tile buffer
   Stage<DK, NW, TILE> stK[PARTS], stV[PARTS];
   const int ntiles = ((L + TR - 1) / TR + PARTS - 1) / PARTS;  // tiles of one part: part p walks tiles p ntiles ..
   auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * TBUF; };
-  // key mask of a tile as an ADDITIVE term of the soft-max argument (0 or -inf per key), read back one float4 per register
-  // quadruple: no bit extraction and no select per element
-  auto publish_mask = [&](int k0, int buf, int pt) __attribute__((always_inline)) {
-    if (tid < TR) {
-      const int key = k0 + tid;
-      sBias[buf][pt][tid] = (key < L && sq[key < L ? key : 0] != PTAMD_PAD_ID) ? 0.f : -INFINITY;
-    }
-  };
   TileRows<DK, NW> rows[PARTS];
   Stage<DK, NW, TILE> nxK[PARTS], nxV[PARTS];  // loads run two tiles ahead of the arithmetic (attention_split.hip)
 #pragma unroll
@@ -459,7 +560,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
     stV[pt].load(base + 2 * D, toff);
     stK[pt].store(tile(0, pt), sInvK[0][pt], pt * ntiles * TR, L, tid);
     stV[pt].store(tile(0, pt) + TE, sInvV[0][pt], pt * ntiles * TR, L, tid);
-    publish_mask(pt * ntiles * TR, 0, pt);
+    publish_key_mask(sBias[0][pt], sq, pt * ntiles * TR, L, tid);
     const auto toff2 = rows[pt].next();
     stK[pt].load(base + D, toff2);
     stV[pt].load(base + 2 * D, toff2);
@@ -478,93 +579,32 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
     }
     const float4 ik4 = *reinterpret_cast<const float4 *>(&sInvK[cur][part][4 * lh]);  // the four key groups of this lane half
     const float4 iva = *reinterpret_cast<const float4 *>(&sInvV[cur][part][0]), ivb = *reinterpret_cast<const float4 *>(&sInvV[cur][part][4]);
-    f32x16 s;
+    fwd_tile_step<DK>(
+        state, qf, cq, ik4, iva, ivb, sBias[cur][part], k0, dk_, q_part, p_drop, keep_bits != nullptr, lh,
+        [&](int ks, f16x8 (&f)[2]) __attribute__((always_inline)) {
+          if constexpr (HALVES<DK> == 1) TILE::frag_rows(sK, ks, lane, f);  // (dk = 64 / 32 written out: same instructions)
+          else tile_frag_rows<TILE>(sK, ks, lane, f);
+        },
+        [&](int kb, int t, f16x8 (&f)[2]) __attribute__((always_inline)) {
+          if constexpr (HALVES<DK> == 1) TILE::frag_cols(sV, kb, 32 * t, lane, f);
+          else tile_frag_cols<TILE>(sV, kb, t, lane, f);
+        },
+        [&]() __attribute__((always_inline)) {
+          if (more) {  // scale + split + store the next tile(s) into the other buffer while the soft-max runs
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st) {  // S^T[key][q] = K Q^T (scaled operands)
-      f16x8 kf[2];
-      if constexpr (HALVES<DK> == 1) TILE::frag_rows(sK, st, lane, kf);  // (dk = 64 / 32 written out: same instructions)
-      else tile_frag_rows<TILE>(sK, st, lane, kf);
-      s = mfma3(kf, qf[st], s);
-    }
-    if (more) {  // scale + split + store the next tile(s) into the other buffer while the soft-max runs
-#pragma unroll
-      for (int pt = 0; pt < PARTS; ++pt) {
-        const int kn = (pt * ntiles + kt + 1) * TR;
-        stK[pt].store(tile(cur ^ 1, pt), sInvK[cur ^ 1][pt], kn, L, tid);
-        stV[pt].store(tile(cur ^ 1, pt) + TE, sInvV[cur ^ 1][pt], kn, L, tid);
-        publish_mask(kn, cur ^ 1, pt);
-      }
-    }
-    const float cu[4] = {cq * ik4.x, cq * ik4.y, cq * ik4.z, cq * ik4.w};
-    float mt = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 b4 = *reinterpret_cast<const float4 *>(&sBias[cur][part][8 * j + 4 * lh]);
-      const float bias[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {  // (s cu is finite - a masked group of zero rows has s = cu = 0 - so the sum is -inf, not NaN)
-        s[4 * j + e] = fmaf(s[4 * j + e], cu[j], bias[e]);
-        mt = fmaxf(mt, s[4 * j + e]);
-      }
-    }
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float m_new = fmaxf(m_run, mt);
-    const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s[r] = __builtin_amdgcn_exp2f(s[r] - m_safe);
-      ps += s[r];
-    }
-    l_run = l_run * alpha + ps;
-    m_run = m_new;
-    // common scale of the V groups: O accumulates  sum P (iv_g / v_run) 2^14 * (V sv_g)  =  (2^14 / v_run) sum P V
-    const float vt = fmaxf(fmaxf(fmaxf(iva.x, iva.y), fmaxf(iva.z, iva.w)), fmaxf(fmaxf(ivb.x, ivb.y), fmaxf(ivb.z, ivb.w)));
-    float resc = alpha;
-    if (vt > v_run) {
-      resc *= v_run * inv_pow2(vt);
-      v_run = vt;
-    }
-    if (__builtin_amdgcn_ballot_w64(resc != 1.f)) {  // wave-uniform: after the first tiles neither maximum moves often
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {  // scalar multiplies, kept apart: packed f32 VALU stalls the matrix pipe
-          float v = o[t][r] * resc;
-          asm volatile("" : "+v"(v));
-          o[t][r] = v;
-        }
-    }
-    const float vn = inv_pow2(v_run);
-    const float4 ivh = lh ? ivb : iva;
-    const float fv[4] = {ivh.x * TWO14 * vn, ivh.y * TWO14 * vn, ivh.z * TWO14 * vn, ivh.w * TWO14 * vn};  // <= 2^14
-    if (p_drop > 0.f) {  // the 1 / (1 - p) is applied to O at the end
-      if (keep_bits) {   // (uniform) the decisions also go out for the fused backward kernel: attn_dropout.h
-        const uint32_t word = attn_drop_keys_in_rows_export(dk_, q_part, k0, lh, s);
-        const int lk = (L + 31) & ~31;
-        if (lane < 32 && k0 + lane < lk && q0 < lk)   // (a workgroup's last wavefronts may hold no query at all)
-          keep_bits[((size_t)(b * H + h) * (lk >> 5) + (q0 >> 5)) * lk + k0 + lane] = word;
-      } else {
-        attn_drop_keys_in_rows(dk_, q_part, k0, lh, s);
-      }
-    }
-    // O^T[d][q] += V^T[d][key] P^T[key][q]: the accumulator rows of s are already in the k order of frag_cols
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const float x[8] = {s[8 * m], s[8 * m + 1], s[8 * m + 2], s[8 * m + 3], s[8 * m + 4], s[8 * m + 5], s[8 * m + 6], s[8 * m + 7]};
-      f16x8 pf[2];
-      split8g(x, fv[2 * m], fv[2 * m + 1], pf);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        f16x8 vf[2];
-        if constexpr (HALVES<DK> == 1) TILE::frag_cols(sV, 16 * m, 32 * t, lane, vf);
-        else tile_frag_cols<TILE>(sV, 16 * m, t, lane, vf);
-        o[t] = mfma3(vf, pf, o[t]);
-      }
-    }
+            for (int pt = 0; pt < PARTS; ++pt) {
+              const int kn = (pt * ntiles + kt + 1) * TR;
+              stK[pt].store(tile(cur ^ 1, pt), sInvK[cur ^ 1][pt], kn, L, tid);
+              stV[pt].store(tile(cur ^ 1, pt) + TE, sInvV[cur ^ 1][pt], kn, L, tid);
+              publish_key_mask(sBias[cur ^ 1][pt], sq, kn, L, tid);
+            }
+          }
+        },
+        [&](uint32_t word) __attribute__((always_inline)) {  // the layout pads L to whole tiles of keys and of queries
+          const int lk = (L + 31) & ~31;
+          if (lane < 32 && k0 + lane < lk && q0 < lk)   // (a workgroup's last wavefronts may hold no query at all)
+            keep_bits[((size_t)(b * H + h) * (lk >> 5) + (q0 >> 5)) * lk + k0 + lane] = word;
+        });
 #pragma unroll
     for (int pt = 0; pt < PARTS; ++pt) {
       stK[pt] = nxK[pt];
@@ -580,13 +620,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
     constexpr int XCH = (NT * 16 + 3) * 64;
     float *xch = reinterpret_cast<float *>(smem) + ((part > 0 ? part - 1 : 0) * NG + grp) * XCH + lane;
     if (part > 0) {
-      xch[0] = m_run;
-      xch[64] = l_run;
-      xch[128] = v_run;
+      xch[0] = state.m_run;
+      xch[64] = state.l_run;
+      xch[128] = state.v_run;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) xch[(3 + t * 16 + r) * 64] = o[t][r];
+        for (int r = 0; r < 16; ++r) xch[(3 + t * 16 + r) * 64] = state.o[t][r];
     }
     __syncthreads();
     if (part > 0) return;
@@ -594,34 +634,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
     for (int k = 0; k < PARTS - 1; ++k) {
       const float *x = xch + (size_t)k * NG * XCH;
       const float m1 = x[0], l1 = x[64], v1 = x[128];
-      const float m = fmaxf(m_run, m1), ms = m == -INFINITY ? 0.f : m;
-      const float a0 = __builtin_amdgcn_exp2f(m_run - ms), a1 = __builtin_amdgcn_exp2f(m1 - ms);
-      const float vm = fmaxf(v_run, v1), ivm = inv_pow2(vm);  // common V scale (powers of two; 0 only if both are)
-      const float f0 = a0 * (v_run * ivm), f1 = a1 * (v1 * ivm);
+      const float m = fmaxf(state.m_run, m1), ms = m == -INFINITY ? 0.f : m;
+      const float a0 = __builtin_amdgcn_exp2f(state.m_run - ms), a1 = __builtin_amdgcn_exp2f(m1 - ms);
+      const float vm = fmaxf(state.v_run, v1), ivm = inv_pow2(vm);  // common V scale (powers of two; 0 only if both are)
+      const float f0 = a0 * (state.v_run * ivm), f1 = a1 * (v1 * ivm);
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] = o[t][r] * f0 + x[(3 + t * 16 + r) * 64] * f1;
-      l_run = l_run * a0 + l1 * a1;
-      m_run = m;
-      v_run = vm;
+        for (int r = 0; r < 16; ++r) state.o[t][r] = fmaf(state.o[t][r], f0, x[(3 + t * 16 + r) * 64] * f1);
+      state.l_run = fmaf(state.l_run, a0, l1 * a1);  // (which product is fused is spelled out: the bits do not hang on the compiler's choice)
+      state.m_run = m;
+      state.v_run = vm;
     }
   }
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  // soft-max normalisation, dropout scale and the common V scale in one factor
-  const float inv = (p_drop > 0.f ? dk_.ks : 1.f) * v_run * INV_TWO14 / l_tot;
-  if (q_ok) {
-    float *op = out + (size_t)(b * L + q) * D + h * DK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(op + d) =
-            make_float4(o[t][4 * g] * inv, o[t][4 * g + 1] * inv, o[t][4 * g + 2] * inv, o[t][4 * g + 3] * inv);
-      }
-    if (lh == 0) lse[((size_t)b * H + h) * L + q] = (m_run + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-  }
+  state.finish(p_drop > 0.f ? dk_.ks : 1.f, q_ok, lh, out + (size_t)(b * L + q) * D + h * DK, lse + ((size_t)b * H + h) * L + q);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -629,8 +655,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(FWD_WAV
 // product's epilogue wrote is byte for byte the LDS image of a tile, so a stage of K and V is filled by 1-KiB LDS-DMA pieces
 // (two per wavefront and 32-key tile) instead of two float4 loads, a group maximum, a split and two ds_write per thread and
 // tile - the staging that was a fifth of the kernel's VALU instructions (profiles/tools/isa_mix.py: 570 -> 491 per tile and
-// wavefront, all paths).  Same scaling groups, same split arithmetic, same soft-max, same dropout decisions: bit-identical to
-// attn_fwd_f16x2_kernel<64, 8, 1> on the fp32 K / V those planes were made from.
+// wavefront, all paths).  The planes hold the scaling groups and the split of Stage::store, and every tile goes through
+// fwd_tile_step, the function attn_fwd_f16x2_kernel calls (state, soft-max, dropout decisions, products and FwdState::finish are
+// one piece of code, only the fragment readers and the keep_bits index differ): bit-identical to attn_fwd_f16x2_kernel<64, 8, 1>
+// on the fp32 K / V those planes were made from (tests/test_gpu_kv_planes.py).
 // A stage is TPS = 2 tiles (64 keys): THREE stage buffers, the pieces of stage s + 2 issued at the end of stage s and a
 // counted wait (this wavefront's pieces of that stage may stay in flight) in front of a raw s_barrier - HBM latency is two
 // stages of arithmetic, and there is ONE barrier per stage: half as many as the fp32 kernel, whose eight wavefronts meet at
@@ -703,12 +731,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
   f16x8 qf[KS][2];
   const float iq = load_row_scaled<KS>(base, D3, min(q, L - 1), q_ok, lh, qf);
   const float cq = scale * LOG2E * iq;
-  f32x16 o[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f, v_run = 0.f;
+  FwdState<NT> state;
+  state.init();
   publish(0);
   if (nstages > 1) {
     issue(1, 1);
@@ -734,79 +758,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
       const char *sK = stage0 + buf * STAGE + u * 2 * ptkv::TILE_BYTES, *sV = sK + ptkv::TILE_BYTES;
       const float4 ik4 = *reinterpret_cast<const float4 *>(&sInvK[cur][u][4 * lh]);
       const float4 iva = *reinterpret_cast<const float4 *>(&sInvV[cur][u][0]), ivb = *reinterpret_cast<const float4 *>(&sInvV[cur][u][4]);
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-      for (int k = 0; k < KS; ++k) {  // S^T[key][q] = K Q^T (scaled operands)
-        f16x8 kf[2];
-        KvTile::frag_rows(sK, k, lane, kf);
-        s = mfma3(kf, qf[k], s);
-      }
-      const float cu[4] = {cq * ik4.x, cq * ik4.y, cq * ik4.z, cq * ik4.w};
-      float mt = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 b4 = *reinterpret_cast<const float4 *>(&sBias[cur][u][8 * j + 4 * lh]);
-        const float bias[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          s[4 * j + e] = fmaf(s[4 * j + e], cu[j], bias[e]);
-          mt = fmaxf(mt, s[4 * j + e]);
-        }
-      }
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float m_new = fmaxf(m_run, mt);
-      const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s[r] = __builtin_amdgcn_exp2f(s[r] - m_safe);
-        ps += s[r];
-      }
-      l_run = l_run * alpha + ps;
-      m_run = m_new;
-      const float vt = fmaxf(fmaxf(fmaxf(iva.x, iva.y), fmaxf(iva.z, iva.w)), fmaxf(fmaxf(ivb.x, ivb.y), fmaxf(ivb.z, ivb.w)));
-      float resc = alpha;
-      if (vt > v_run) {
-        resc *= v_run * inv_pow2(vt);
-        v_run = vt;
-      }
-      if (__builtin_amdgcn_ballot_w64(resc != 1.f)) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float v = o[t][r] * resc;
-            asm volatile("" : "+v"(v));
-            o[t][r] = v;
-          }
-      }
-      const float vn = inv_pow2(v_run);
-      const float4 ivh = lh ? ivb : iva;
-      const float fv[4] = {ivh.x * TWO14 * vn, ivh.y * TWO14 * vn, ivh.z * TWO14 * vn, ivh.w * TWO14 * vn};
-      if (p_drop > 0.f) {
-        if (keep_bits) {
-          const uint32_t word = attn_drop_keys_in_rows_export(dk_, q_part, k0, lh, s);
-          if (lane < 32 && q0 < L)
-            keep_bits[((size_t)(b * H + h) * (L >> 5) + (q0 >> 5)) * L + k0 + lane] = word;
-        } else {
-          attn_drop_keys_in_rows(dk_, q_part, k0, lh, s);
-        }
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const float x[8] = {s[8 * m], s[8 * m + 1], s[8 * m + 2], s[8 * m + 3], s[8 * m + 4], s[8 * m + 5], s[8 * m + 6], s[8 * m + 7]};
-        f16x8 pf[2];
-        split8g(x, fv[2 * m], fv[2 * m + 1], pf);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          f16x8 vf[2];
-          KvTile::frag_cols(sV, 16 * m, 32 * t, lane, vf);
-          o[t] = mfma3(vf, pf, o[t]);
-        }
-      }
+      fwd_tile_step<DK>(
+          state, qf, cq, ik4, iva, ivb, sBias[cur][u], k0, dk_, q_part, p_drop, keep_bits != nullptr, lh,
+          [&](int k, f16x8 (&f)[2]) __attribute__((always_inline)) { KvTile::frag_rows(sK, k, lane, f); },
+          [&](int kb, int t, f16x8 (&f)[2]) __attribute__((always_inline)) { KvTile::frag_cols(sV, kb, 32 * t, lane, f); },
+          [] {},  // (nothing is staged by hand here: the next stages arrive by LDS-DMA)
+          [&](uint32_t word) __attribute__((always_inline)) {  // (L is a multiple of 32: no padding of the layout to guard)
+            if (lane < 32 && q0 < L) keep_bits[((size_t)(b * H + h) * (L >> 5) + (q0 >> 5)) * L + k0 + lane] = word;
+          });
     }
     // The pieces of stage st + 2 are this wavefront's LAST memory operations of the stage (behind the decision stores, the small
     // loads and every LDS read): the counted wait then leaves exactly them in flight - stage st + 1, issued a stage ago, has
@@ -819,20 +778,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(PT_ATTN_FWD
     __builtin_amdgcn_s_barrier();
     buf = buf == 2 ? 0 : buf + 1;
   }
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = (p_drop > 0.f ? dk_.ks : 1.f) * v_run * INV_TWO14 / l_tot;
-  if (q_ok) {
-    float *op = out + (size_t)(b * L + q) * D + h * DK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(op + d) =
-            make_float4(o[t][4 * g] * inv, o[t][4 * g + 1] * inv, o[t][4 * g + 2] * inv, o[t][4 * g + 3] * inv);
-      }
-    if (lh == 0) lse[((size_t)b * H + h) * L + q] = (m_run + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-  }
+  state.finish(p_drop > 0.f ? dk_.ks : 1.f, q_ok, lh, out + (size_t)(b * L + q) * D + h * DK, lse + ((size_t)b * H + h) * L + q);
 }
 
 // =================================================================================================== backward
@@ -872,15 +818,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
   float my_delta = 0.f;
   {  // each lane half holds half of the d of its query's row
     const float *gp = d_o + ((size_t)b * L + qc) * D + h * DK, *op = o_fwd + ((size_t)b * L + qc) * D + h * DK;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float4 g4 = *reinterpret_cast<const float4 *>(gp + 16 * st + 8 * lh + 4 * j);
-        const float4 o4 = *reinterpret_cast<const float4 *>(op + 16 * st + 8 * lh + 4 * j);
-        my_delta += g4.x * o4.x + g4.y * o4.y + g4.z * o4.z + g4.w * o4.w;
-      }
-    my_delta += __shfl_xor(my_delta, 32, 64);
+    my_delta = row_delta<KS>(gp, op, lh);
     if (!q_ok) my_delta = 0.f;
     if (q_ok && lh == 0 && part == 0) delta[((size_t)b * H + h) * L + q] = my_delta;
   }
@@ -888,24 +826,13 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
   const float gq = ig * (p_drop > 0.f ? dk_.ks : 1.f);
 
   f32x16 dq[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[t][r] = 0.f;
+  acc_zero(dq);
   float bscale = BSCALE0;  // common power of two of the dS operand (per query = per accumulator column)
 
   Stage<DK, NW> stK[PARTS], stV[PARTS];
   const int ntiles = ((L + TR - 1) / TR + PARTS - 1) / PARTS;  // tiles of one part: part p walks tiles p ntiles ..
   constexpr int TE = HALVES<DK> * Tile2::ELEMS;  // f16 elements of one staged tile
   auto tile = [&](int buf, int pt) __attribute__((always_inline)) { return smem + (buf * PARTS + pt) * (HALVES<DK> * BUF); };
-  // key mask of a tile as an ADDITIVE term of the soft-max argument (0 or -inf per key), read back one float4 per register
-  // quadruple: no bit extraction and no select per element
-  auto publish_mask = [&](int k0, int buf, int pt) __attribute__((always_inline)) {
-    if (tid < TR) {
-      const int key = k0 + tid;
-      sBias[buf][pt][tid] = (key < L && sq[key < L ? key : 0] != PTAMD_PAD_ID) ? 0.f : -INFINITY;
-    }
-  };
   TileRows<DK, NW> rows[PARTS];
   Stage<DK, NW> nxK[PARTS], nxV[PARTS];
 #pragma unroll
@@ -916,7 +843,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
     stV[pt].load(base + 2 * D, toff);
     stK[pt].store(tile(0, pt), sInvK[0][pt], pt * ntiles * TR, L, tid);
     stV[pt].store(tile(0, pt) + TE, sInvV[0][pt], pt * ntiles * TR, L, tid);
-    publish_mask(pt * ntiles * TR, 0, pt);
+    publish_key_mask(sBias[0][pt], sq, pt * ntiles * TR, L, tid);
     const auto toff2 = rows[pt].next();
     stK[pt].load(base + D, toff2);
     stV[pt].load(base + 2 * D, toff2);
@@ -957,7 +884,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
         const int kn = (pt * ntiles + kt + 1) * TR;
         stK[pt].store(tile(cur ^ 1, pt), sInvK[cur ^ 1][pt], kn, L, tid);
         stV[pt].store(tile(cur ^ 1, pt) + TE, sInvV[cur ^ 1][pt], kn, L, tid);
-        publish_mask(kn, cur ^ 1, pt);
+        publish_key_mask(sBias[cur ^ 1][pt], sq, kn, L, tid);
       }
     }
     const float ik[4] = {ik4.x, ik4.y, ik4.z, ik4.w}, iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
@@ -975,7 +902,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
       const int j = r >> 2;
       // (the mask goes into the ARGUMENT, exp2(-inf) = 0: 0 or -inf per key, added to -lse)
       const float4 b4 = *reinterpret_cast<const float4 *>(&sBias[cur][part][8 * j + 4 * lh]);
-      const float nb = ((r & 3) == 0 ? b4.x : (r & 3) == 1 ? b4.y : (r & 3) == 2 ? b4.z : b4.w) - my_lse2;
+      const float nb = f4_at(b4, r) - my_lse2;
       const float p = __builtin_amdgcn_exp2f(fmaf(s[r], cu[j], nb));
       const float g = dp[r] * ug[j];
       s[r] = p * (g - my_delta) * wk[j];
@@ -984,14 +911,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
     wmax = fmaxf(wmax, __shfl_xor(wmax, 32, 64));
     const float ratio = online_scale(wmax, bscale);
     if (__builtin_amdgcn_ballot_w64(ratio != 1.f)) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float v = dq[t][r] * ratio;
-          asm volatile("" : "+v"(v));
-          dq[t][r] = v;
-        }
+      acc_scale(dq, ratio);
     }
     // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
 #pragma unroll
@@ -1035,14 +955,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
   const bool writer = part == 0;
   if (q_ok && writer) {
     float *op = dqkv + (size_t)(b * L + q) * D3 + h * DK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(op + d) =
-            make_float4(dq[t][4 * g] * un, dq[t][4 * g + 1] * un, dq[t][4 * g + 2] * un, dq[t][4 * g + 3] * un);
-      }
+    acc_store_rows<DK>(op, dq, lh, un);
   }
   if (row_scale) {
     float am = 0.f;
@@ -1092,10 +1005,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
   const float ck = scale * LOG2E * ikl, gk = ivl * ks;
 
   f32x16 dk[NT], dv[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dk[t][r] = dv[t][r] = 0.f;
+  acc_zero(dk);
+  acc_zero(dv);
   float bscale = BSCALE0;  // common power of two of the dS operand (per key = per accumulator column)
   float g_run = 0.f;       // largest inverse dO group scale so far (wavefront-uniform)
 
@@ -1183,18 +1094,11 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
       }
     }
     // common scale of the dO groups: dV accumulates (2^14 / g_run) sum Pd dO
-    const float gt = fmaxf(fmaxf(fmaxf(iga.x, iga.y), fmaxf(iga.z, iga.w)), fmaxf(fmaxf(igb.x, igb.y), fmaxf(igb.z, igb.w)));
+    const float gt = max8(iga, igb);
     if (gt > g_run) {  // (wavefront-uniform)
       const float resc = g_run * inv_pow2(gt);
       g_run = gt;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float v = dv[t][r] * resc;
-          asm volatile("" : "+v"(v));
-          dv[t][r] = v;
-        }
+      acc_scale(dv, resc);
     }
     const float gn = inv_pow2(g_run);  // (2^127 while every dO group seen so far is zero: multiplied LAST, after 0 * 2^14)
     const float4 igh = lh ? igb : iga;
@@ -1225,8 +1129,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
       // L carry lse = +inf, so the row mask costs nothing per element and the key mask is a loop-invariant select)
       const float4 l4 = *reinterpret_cast<const float4 *>(&sLse[cur][part][8 * j + 4 * lh]);
       const float4 d4 = *reinterpret_cast<const float4 *>(&sDel[cur][part][8 * j + 4 * lh]);
-      const float my_l = (r & 3) == 0 ? l4.x : (r & 3) == 1 ? l4.y : (r & 3) == 2 ? l4.z : l4.w;
-      const float my_d = (r & 3) == 0 ? d4.x : (r & 3) == 1 ? d4.y : (r & 3) == 2 ? d4.z : d4.w;
+      const float my_l = f4_at(l4, r);
+      const float my_d = f4_at(d4, r);
       const float p = __builtin_amdgcn_exp2f(k_valid ? fmaf(s[r], cu[j], -my_l) : -INFINITY);
       float g = dp[r] * ug[j], pk = p;
       if (p_drop > 0.f) {
@@ -1240,14 +1144,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
     wmax = fmaxf(wmax, __shfl_xor(wmax, 32, 64));
     const float ratio = online_scale(wmax, bscale);
     if (__builtin_amdgcn_ballot_w64(ratio != 1.f)) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float v = dk[t][r] * ratio;
-          asm volatile("" : "+v"(v));
-          dk[t][r] = v;
-        }
+      acc_scale(dk, ratio);
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -1314,16 +1211,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(BWD_
   }
   if (k_ok && writer) {
     float *okp = dqkv + (size_t)(b * L + key) * D3 + D + h * DK, *ovp = okp + D;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(okp + d) =
-            make_float4(dk[t][4 * g] * uk, dk[t][4 * g + 1] * uk, dk[t][4 * g + 2] * uk, dk[t][4 * g + 3] * uk);
-        *reinterpret_cast<float4 *>(ovp + d) =
-            make_float4(dv[t][4 * g] * uv, dv[t][4 * g + 1] * uv, dv[t][4 * g + 2] * uv, dv[t][4 * g + 3] * uv);
-      }
+    acc_store_rows<DK>(okp, dk, lh, uk);
+    acc_store_rows<DK>(ovp, dv, lh, uv);
   }
 }
 

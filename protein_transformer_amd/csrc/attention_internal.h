@@ -2,7 +2,9 @@
 // attention_split.hip (bf16x3) and attention_f16x2.hip (f16x2).  The arguments of one call as plain structs - filled once by
 // ptamd_attention_fwd / ptamd_attention_bwd and passed by reference down to the launch, so no launcher restates a positional
 // list of look-alike pointers -, the prototypes of what one unit calls in another, the one way a kernel is launched, which
-// arithmetic family serves a (dk, arith), and the few device helpers all the kernels use.
+// arithmetic family serves a (dk, arith), and the device helpers all the kernels use: fast_exp, crow, and what every kernel does
+// to its transposed 32 x 32 accumulators - acc_zero, acc_scale (the rescale by a running factor), acc_store_rows (a lane's row
+// of the result) -, row_delta (delta[q] = sum_d dO O of a lane's query), max8 and f4_at.
 #pragma once
 #include <type_traits>
 
@@ -82,3 +84,61 @@ using ptsplit::f32x16;  // a 32 x 32 MFMA C tile: 16 registers per lane
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 // row index inside a 32x32 MFMA C tile held by (register r, lane half lh)
 __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// ---- accumulators acc[NT] of a TRANSPOSED result (O^T, dQ^T, dK^T, dV^T): tile t holds d = 32 t .. 32 t + 31 in its rows, a
+// lane (l31, lh) the column of its query or key - registers 4 g .. 4 g + 3 are d = 32 t + 8 g + 4 lh + 0..3 (crow)
+template <int NT>
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+}
+// acc *= f, for the rescale by a running maximum or scale inside a tile loop: scalar multiplies, kept apart by an empty asm
+// (packed f32 VALU, which the compiler would form of them, stalls the matrix pipe)
+template <int NT>
+__device__ __forceinline__ void acc_scale(f32x16 (&acc)[NT], float f) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float v = acc[t][r] * f;
+      asm volatile("" : "+v"(v));
+      acc[t][r] = v;
+    }
+}
+// the lane's half of row `row` (DK floats: the query's or key's row of the result) = its accumulator column times f, one float4
+// per register quadruple; head sizes below 32 fill a part of the one accumulator
+template <int DK, int NT>
+__device__ __forceinline__ void acc_store_rows(float *__restrict__ row, const f32x16 (&acc)[NT], int lh, float f = 1.f) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = t * 32 + 8 * g + 4 * lh;
+      if (DK >= 32 || d < DK)
+        *reinterpret_cast<float4 *>(row + d) =
+            make_float4(acc[t][4 * g] * f, acc[t][4 * g + 1] * f, acc[t][4 * g + 2] * f, acc[t][4 * g + 3] * f);
+    }
+}
+// sum_d g[d] o[d] over a row of 16 KS floats, in both lane halves: each holds d = 16 st + 8 lh + 0..7 of its query's row
+template <int KS>
+__device__ __forceinline__ float row_delta(const float *__restrict__ gp, const float *__restrict__ op, int lh) {
+  float sum = 0.f;
+#pragma unroll
+  for (int st = 0; st < KS; ++st)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float4 g4 = *reinterpret_cast<const float4 *>(gp + 16 * st + 8 * lh + 4 * j);
+      const float4 o4 = *reinterpret_cast<const float4 *>(op + 16 * st + 8 * lh + 4 * j);
+      sum += g4.x * o4.x + g4.y * o4.y + g4.z * o4.z + g4.w * o4.w;
+    }
+  return sum + __shfl_xor(sum, 32, 64);
+}
+__device__ __forceinline__ float max8(const float4 &a, const float4 &b) {
+  return fmaxf(fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)), fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
+}
+// component i & 3 of v (i a constant after unrolling: no select is left)
+__device__ __forceinline__ float f4_at(const float4 &v, int i) {
+  return (i & 3) == 0 ? v.x : (i & 3) == 1 ? v.y : (i & 3) == 2 ? v.z : v.w;
+}

@@ -94,10 +94,7 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   load_row_split(base, D3, min(q, L - 1), q_ok, lh, qf);
 
   f32x16 o[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  acc_zero(o);
   float m_run = -INFINITY, l_run = 0.f;
 
   Stage32<DK> stK, stV;
@@ -169,14 +166,7 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
     l_run = l_run * alpha + ps;
     m_run = m_new;
     if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {  // wave-uniform: after the first tiles the running maximum rarely moves
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {  // scalar multiplies, kept apart: packed f32 VALU stalls the matrix pipe
-          float v = o[t][r] * alpha;
-          asm volatile("" : "+v"(v));
-          o[t][r] = v;
-        }
+      acc_scale(o, alpha);
     }
     if (p_drop > 0.f) {
       const uint32_t keep = attn_keep_bits_keys_in_rows(dk_, q_part, k0, lh);
@@ -205,14 +195,7 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const float inv = (p_drop > 0.f ? dk_.ks : 1.f) / l_tot;  // softmax normalisation and the dropout scale in one factor
   if (q_ok) {
     float *op = out + (size_t)(b * L + q) * D + h * DK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(op + d) =
-            make_float4(o[t][4 * g] * inv, o[t][4 * g + 1] * inv, o[t][4 * g + 2] * inv, o[t][4 * g + 3] * inv);
-      }
+    acc_store_rows<DK>(op, o, lh, inv);
     if (lh == 0) lse[((size_t)b * H + h) * L + q] = m_run + logf(l_tot);
   }
 }
@@ -247,24 +230,13 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   float my_delta = 0.f;
   {  // each lane half holds half of the d of its query's row
     const float *gp = d_o + ((size_t)b * L + qc) * D + h * DK, *op = o_fwd + ((size_t)b * L + qc) * D + h * DK;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float4 g4 = *reinterpret_cast<const float4 *>(gp + 16 * st + 8 * lh + 4 * j);
-        const float4 o4 = *reinterpret_cast<const float4 *>(op + 16 * st + 8 * lh + 4 * j);
-        my_delta += g4.x * o4.x + g4.y * o4.y + g4.z * o4.z + g4.w * o4.w;
-      }
-    my_delta += __shfl_xor(my_delta, 32, 64);
+    my_delta = row_delta<KS>(gp, op, lh);
     if (!q_ok) my_delta = 0.f;
     if (q_ok && lh == 0) delta[((size_t)b * H + h) * L + q] = my_delta;
   }
 
   f32x16 dq[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dq[t][r] = 0.f;
+  acc_zero(dq);
 
   Stage32<DK> stK, stV;
   const int ntiles = (L + TR - 1) / TR;
@@ -339,13 +311,7 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
   if (q_ok) {
     float *op = dqkv + (size_t)(b * L + q) * D3 + h * DK;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(op + d) = make_float4(dq[t][4 * g], dq[t][4 * g + 1], dq[t][4 * g + 2], dq[t][4 * g + 3]);
-      }
+    acc_store_rows<DK>(op, dq, lh);
   }
 }
 
@@ -377,10 +343,8 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   load_row_split(base + 2 * D, D3, min(key, L - 1), k_ok, lh, vf);
 
   f32x16 dk[NT], dv[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dk[t][r] = dv[t][r] = 0.f;
+  acc_zero(dk);
+  acc_zero(dv);
 
   Stage32<DK> stQ, stG;
   const int ntiles = (L + TR - 1) / TR;
@@ -471,14 +435,8 @@ __global__ __launch_bounds__(NTHR, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
   if (k_ok) {
     float *okp = dqkv + (size_t)(b * L + key) * D3 + D + h * DK, *ovp = okp + D;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = t * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<float4 *>(okp + d) = make_float4(dk[t][4 * g], dk[t][4 * g + 1], dk[t][4 * g + 2], dk[t][4 * g + 3]);
-        *reinterpret_cast<float4 *>(ovp + d) = make_float4(dv[t][4 * g], dv[t][4 * g + 1], dv[t][4 * g + 2], dv[t][4 * g + 3]);
-      }
+    acc_store_rows<DK>(okp, dk, lh);
+    acc_store_rows<DK>(ovp, dv, lh);
   }
 }
 
