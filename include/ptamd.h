@@ -200,6 +200,45 @@ int ptamd_slddt_fwd_bwd(const float *pred_crd, const float *true_crd, const int6
                         float temperature, float *stats, int64_t *npairs, float *dcrd, void *workspace, size_t workspace_bytes,
                         void *stream);
 
+/* Frame aligned point error (FAPE), forward + analytic backward, for a whole batch (csrc/fape.hip): the training loss
+ * `-l fape`.  The reference has no counterpart, and every other structural loss here is a function of internal distances, blind
+ * to a mirror image; this is the loss of Jumper et al., "Highly accurate protein structure prediction with AlphaFold", Nature
+ * 596:583-589 (2021), supplementary algorithms 21 (a frame from three points) and 28 (FAPE), over backbone frames and all atoms.
+ *   Atoms.  Per protein, exactly those of ptamd_lddt and ptamd_slddt_fwd_bwd: slots of non-pad residues whose true coordinate
+ *   has no NaN.
+ *   Frames.  The non-pad residues whose slots 0, 1, 2 (N, CA, C) are all present in the truth and whose TRUE frame is not
+ *   degenerate.  Algorithm 21 with origin t = CA: v1 = C - CA, v2 = N - CA, e1 = v1 / |v1|, u2 = v2 - e1 (e1 . v2),
+ *   e2 = u2 / |u2|, e3 = e1 x e2, R = (e1 e2 e3); degenerate when |v1|^2 <= 1e-8 A^2 or |u2|^2 <= 1e-8 A^2.  Which frames exist
+ *   depends on the truth only.  (Evaluated in fp64 on the fp32 coordinates and rounded once.)
+ *   Pair.  For every ordered (frame i, atom j), atoms of residue i included: x_ij = R_i^T (x_j - t_i) for the prediction and
+ *   likewise for the truth, Delta_ij their difference, d_ij = sqrt(|Delta_ij|^2 + 1e-4 A^2), pair value = min(d_ij, clamp) / Z
+ *   with Z = 10 A.  The clamp test is strict: a pair with d < clamp is unclamped; a clamped pair carries no gradient.  clamp
+ *   must be positive and not NaN; +inf means unclamped.
+ *   Per-protein outputs.  loss_i is the mean of the pair values; npairs_i = frames x atoms and nclamped_i the number of clamped
+ *   pairs, exact 64-bit integers.  A protein with no frame or no atom has loss_i = NaN, both counts 0 and an all-zero gradient.
+ *   It is left out of every mean.
+ *   Gradient.  dcrd = d(loss_i)/d(pred_crd), analytic: each unclamped pair gives R_i Delta_ij / (d_ij Z npairs_i) to atom j,
+ *   and to the predicted N, CA, C of frame i what follows through t_i and through the backward of algorithm 21.  The true frame
+ *   is a constant.  Empty slots and padded residues get zeros.  Prediction and truth go through the same device functions, so a
+ *   prediction whose present atoms equal the truth bit for bit has Delta = 0 exactly: dcrd all zeros, loss_i = 1e-3.
+ *   Unusable predictions.  A present atom whose predicted coordinate is not finite or beyond 1e18 in magnitude, or a predicted
+ *   frame that is degenerate by the same 1e-8 test, makes the whole protein unusable: loss_i = NaN and an all-zero gradient;
+ *   npairs_i is still reported, and nclamped_i = 0 (no pair of it is evaluated).  Nothing traps, other proteins are untouched.
+ *   Batch.  The reported batch value is the mean over the proteins with a finite loss; the back-propagated quantity is the SUM
+ *   over proteins of loss_i, as for every structural loss here (SURVEY A-7): data parallelism stays a plain SUM all-reduce.
+ *   stats [B,2] out = {loss_i, nclamped_i / npairs_i}; npairs, nclamped [B] out (int64); dcrd [B,L*14,3] out, or NULL for the
+ *   forward-only form (no gradient work; the same bits in stats and the counts).
+ * No floating-point atomics and fixed-order partial sums: two runs give the same bits, and a protein's result depends neither on
+ * the batch around it nor on how far its row is padded.  Workspace: a function of (B, L) only - 32 B per atom slot, 100 B per
+ * residue (frame records) and 3 KB per (tile of 64 frames, chunk of 8 tiles of 64 atoms); B = 32, L = 512: 20e6 bytes.  No
+ * getenv, no state between calls.  A bad clamp, a NULL array other than dcrd, B or L <= 0, or L beyond INT_MAX / 28 (the bound
+ * of ptamd_lddt): PTAMD_ERR_BAD_SHAPE; workspace NULL or too small: PTAMD_ERR_WORKSPACE; nothing is launched or written in
+ * either case. */
+size_t ptamd_fape_workspace_bytes(int B, int L);
+int ptamd_fape_fwd_bwd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float clamp,
+                       float *stats, int64_t *npairs, int64_t *nclamped, float *dcrd, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* mse_over_angles x3 (losses.py:175-214; train.py:64-66) in one pass.
  *   pred, truth [T,24]; out[6] = {sum_full, cnt_full, sum_bb, cnt_bb, sum_sc, cnt_sc} (fp32); the workspace holds
  *   the fp64 partial sums of the first pass */

@@ -1,5 +1,6 @@
 // The compacted atom tiles that the lDDT family sweeps: csrc/lddt.hip (the metric) and csrc/slddt.hip (the training loss) read
 // the same records, so which atoms exist - the pad test, the NaN test and slot order - is decided here and nowhere else.
+// csrc/fape.hip (the FAPE training loss) sweeps the same atoms against backbone frames.
 // csrc/drmsd.hip packs differently on purpose (backbone first, an interleaved record) and is not a user of this header.
 #pragma once
 #include <limits.h>
@@ -41,6 +42,18 @@ struct TileLayout {
     atoms = take(end, (size_t)B * nstride * sizeof(Atom8));
     boxes = take(end, (size_t)B * tiles * sizeof(Box8));
     natoms = take(end, (size_t)B * sizeof(int));
+  }
+};
+
+// the record of the two training losses (csrc/slddt.hip, csrc/fape.hip): code = residue << 1 | (predicted coordinate unusable),
+// aux = slot.  Unusable = not finite, or beyond 1e18 (squared differences would not be finite): replaced by 0 and marked, so
+// nothing non-finite enters a sweep.
+constexpr float PRED_MAX = 1.0e18f;
+struct SlotRecord {
+  static __device__ __forceinline__ Atom8 make(float px, float py, float pz, float tx, float ty, float tz, int res, int slot) {
+    const bool bad = !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
+    if (bad) px = py = pz = 0.f;
+    return Atom8{px, py, pz, tx, ty, tz, (res << 1) | (int)bad, slot};
   }
 };
 

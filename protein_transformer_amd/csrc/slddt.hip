@@ -43,16 +43,9 @@ constexpr int CHUNK_TILES = 8;    // column tiles of a work item (<= 64: a lane 
 constexpr int SUB = 16, CF_LD = SUB + 1;   // the coefficient tile is kept for 16 columns at a time: 4.3 KB
 constexpr int FIN_THREADS = 256;
 constexpr int NTHR = 4;           // thresholds 0.5, 1, 2, 4
-constexpr float PRED_MAX = 1.0e18f;
 
-// stage 1, atom_tiles::compact_kernel: code = residue << 1 | (predicted coordinate unusable), -1 behind the last atom; aux = slot
-struct SlotRecord {
-  static __device__ __forceinline__ Atom8 make(float px, float py, float pz, float tx, float ty, float tz, int res, int slot) {
-    const bool bad = !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
-    if (bad) px = py = pz = 0.f;
-    return Atom8{px, py, pz, tx, ty, tz, (res << 1) | (int)bad, slot};
-  }
-};
+// stage 1, atom_tiles::compact_kernel with atom_tiles::SlotRecord: code = residue << 1 | (predicted coordinate unusable), -1
+// behind the last atom; aux = slot
 struct __attribute__((aligned(16))) Item {   // what one work item of the sweep leaves for the finalize kernel
   double eps;        // sum over its scored pairs of the four logistics
   long long pairs;   // its included pairs

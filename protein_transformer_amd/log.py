@@ -22,10 +22,10 @@ _HISTORY = ("drmsd", "combined", "lndrmsd", "mse")
 # evaluation under `train.py --eval_lddt` only (no counterpart in the reference): present in a split's metrics once a batch has
 # reported them, as sum-<k> / n-<k> over the batches with a finite value and epoch-<k> = their mean
 _LDDT = ("lddt-full", "lddt-ca")
-# `train.py -l slddt` only (no counterpart in the reference): the smooth lDDT loss, tracked like the `-full` losses above
-# (batch-<k>, epoch-<k>, epoch-history-slddt) in the runs whose loss it is - the metrics of every other run keep exactly their keys
-_SLDDT = "slddt-full"
-_SLDDT_HISTORY = "epoch-history-slddt"
+# `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
+# above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
+# exactly their keys
+_EXTRA_LOSSES = ("slddt", "fape")
 
 
 class EarlyStoppingCondition(Exception):
@@ -38,27 +38,29 @@ def _num(x):
     return float(x.item()) if hasattr(x, "item") else float(x)
 
 
-def _split_metrics(slddt=False):
-    m = {f"epoch-history-{h}": [] for h in _HISTORY}
-    if slddt:
-        m[_SLDDT_HISTORY] = []
-    return m
+def _split_metrics(extra=()):
+    return {f"epoch-history-{h}": [] for h in _HISTORY + tuple(extra)}
+
+
+def _extra(m):
+    """The extra losses a split's metrics track: those whose history it carries."""
+    return tuple(x for x in _EXTRA_LOSSES if f"epoch-history-{x}" in m)
 
 
 def init_metrics(args):
-    slddt = getattr(args, "loss", None) == "slddt"
-    metrics = {"train": _split_metrics(slddt), "test": _split_metrics(slddt), "history-lr": [], "epoch_last_improved": -1,
+    extra = tuple(x for x in _EXTRA_LOSSES if getattr(args, "loss", None) == x)
+    metrics = {"train": _split_metrics(extra), "test": _split_metrics(extra), "history-lr": [], "epoch_last_improved": -1,
                "best_valid_loss_so_far": np.inf, "last_chkpt_time": time.time(), "n_batches": 0}
     for split in VALID_SPLITS:
-        metrics[f"valid-{split}"] = _split_metrics(slddt)
+        metrics[f"valid-{split}"] = _split_metrics(extra)
     if args.lr_scheduling != "noam":
         metrics["history-lr"] = [0]
     return metrics
 
 
 def reset_metrics_for_epoch(metrics, mode):
-    m = metrics.setdefault(mode, _split_metrics(_SLDDT_HISTORY in metrics.get("train", {})))
-    for k in _TRACKED + ((_SLDDT,) if _SLDDT_HISTORY in m else ()):
+    m = metrics.setdefault(mode, _split_metrics(_extra(metrics.get("train", {}))))
+    for k in _TRACKED + tuple(f"{x}-full" for x in _extra(m)):
         m[f"epoch-{k}"] = m[f"batch-{k}"] = 0
     for k in _LDDT:
         for prefix in ("epoch", "sum", "n"):
@@ -81,11 +83,11 @@ def update_metrics(metrics, losses, mode, src_seq, tracking_loss=None, batch_lev
             m[f"epoch-{k}"] += v
         else:
             m[f"epoch-{k}"] = v                       # the reference overwrites the bb/sc entries (log.py:413-416)
-    if _SLDDT_HISTORY in m:
-        v = _num(losses.get(_SLDDT, float("nan")))
+    for x in _extra(m):
+        v = _num(losses.get(f"{x}-full", float("nan")))
         if batch_level:
-            m[f"batch-{_SLDDT}"] = v
-        m[f"epoch-{_SLDDT}"] += v
+            m[f"batch-{x}-full"] = v
+        m[f"epoch-{x}-full"] += v
     for k in _LDDT:
         if k in losses:                               # a batch without any scored protein reports NaN and is left out
             v = _num(losses[k])
@@ -117,9 +119,9 @@ def update_metrics_end_of_epoch(metrics, mode):
             m[f"epoch-{k}"] = m[f"sum-{k}"] / m[f"n-{k}"] if m[f"n-{k}"] else float("nan")
     for h in _HISTORY:
         m[f"epoch-history-{h}"].append(m[f"epoch-{h}-full"])
-    if _SLDDT_HISTORY in m:
-        m[f"epoch-{_SLDDT}"] /= n
-        m[_SLDDT_HISTORY].append(m[f"epoch-{_SLDDT}"])
+    for x in _extra(m):
+        m[f"epoch-{x}-full"] /= n
+        m[f"epoch-history-{x}"].append(m[f"epoch-{x}-full"])
     return metrics
 
 

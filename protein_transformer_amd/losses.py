@@ -107,6 +107,27 @@ def slddt_forward_backward(crd, true_crds, seq, need_grad=True, cutoff=15.0, tem
     return stats, npairs, dcrd
 
 
+# ----------------------------------------------------------------------------- FAPE
+def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
+    """Frame aligned point error of a batch (csrc/fape.hip; definition in include/ptamd.h; no counterpart in the reference).
+    crd, true_crds [B,L*14,3], seq [B,L]; `clamp` in Angstrom, float("inf") = unclamped.  Returns (stats [B,2] = {loss_i,
+    nclamped_i / npairs_i}, npairs [B] int64, nclamped [B] int64, d(loss_i)/d(crd) or None); a protein without a frame or an atom,
+    or with an unusable prediction, has a NaN loss and a zero gradient.  No host synchronisation."""
+    _lib.require_gpu(crd, true_crds, seq)
+    B, L = seq.shape
+    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
+    npairs = torch.empty(B, dtype=torch.int64, device=seq.device)
+    nclamped = torch.empty(B, dtype=torch.int64, device=seq.device)
+    dcrd = torch.empty_like(crd) if need_grad else None
+    ws = _lib.workspace("fape", _lib.lib().ptamd_fape_workspace_bytes(B, L), seq.device)
+    rc = _lib.lib().ptamd_fape_fwd_bwd(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(seq), B, L, float(clamp), _lib.ptr(stats),
+                                       _lib.ptr(npairs), _lib.ptr(nclamped), _lib.ptr(dcrd), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "fape_fwd_bwd")
+    return stats, npairs, nclamped, dcrd
+
+
 class _DrmsdFn(torch.autograd.Function):
     """drmsd(a, b) for two [n,3] point sets, differentiable in a."""
 
@@ -165,7 +186,7 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
     return generate_coords(angles, seq)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None):
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None, fape=None):
     """Device-resident core of compute_batch_drmsd: no host synchronisation.
 
     Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
@@ -181,27 +202,37 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     d(sum_i slddt_i)/d(pred_sincos), `stats` are still the dRMSD statistics (taken forward-only on the same coordinates, so logs
     stay comparable between runs), and the per-protein smooth-lDDT losses [B] (NaN for a protein without an included pair) are
     appended to the returned tuple as its last value.
+
+    `fape` = clamp in Angstrom (`train.py -l fape`; None: everything above is unchanged): the same path with the frame aligned
+    point error of csrc/fape.hip in the place of the smooth lDDT - the gradient is d(sum_i fape_i)/d(pred_sincos), `stats` the
+    forward-only dRMSD statistics, and the per-protein FAPE losses [B] (NaN for a protein without a frame) are appended last.
     """
+    assert slddt is None or fape is None, "one structural loss at a time"
     if slddt is not None:
         assert not backbone_only, "the smooth lDDT loss is an all-atom loss"
+    if fape is not None:
+        assert not backbone_only, "FAPE needs every atom (a backbone FAPE does not exist here)"
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
     crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
-    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward and slddt is None,
-                                         backbone_only=backbone_only)
+    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs,
+                                         need_grad=do_backward and slddt is None and fape is None, backbone_only=backbone_only)
     sl = None
     if slddt is not None:
         sl_stats, _, dcrd = slddt_forward_backward(crd, true_crds, input_seqs, need_grad=do_backward, cutoff=slddt[0],
                                                    temperature=slddt[1])
         sl = sl_stats[:, 0]
+    if fape is not None:
+        fa_stats, _, _, dcrd = fape_forward_backward(crd, true_crds, input_seqs, need_grad=do_backward, clamp=fape)
+        sl = fa_stats[:, 0]
     grad = None
     if do_backward:
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
     out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
-    return out if slddt is None else out + (sl,)
+    return out if sl is None else out + (sl,)
 
 
 # ----------------------------------------------------------------------------- statistics hand-over
@@ -238,10 +269,13 @@ class LossReport:
     # [19:21] sums of the finite lddt-full, lddt-ca  [21:23] proteins with a finite lddt-full, lddt-ca (--eval_lddt; else 0)
     # [23] sum of the finite smooth-lDDT losses  [24] proteins with one (-l slddt; else 0)
     _NVEC = 25
+    # behind them: [25] sum of the finite FAPE losses  [26] proteins with one (-l fape; else 0)
+    _NFAPE = 2
 
-    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None, slddt=None):
+    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
-        `slddt`: per-protein smooth-lDDT losses [B] of batch_loss(..., slddt=...) (`-l slddt`) or None."""
+        `slddt`: per-protein smooth-lDDT losses [B] of batch_loss(..., slddt=...) (`-l slddt`) or None.
+        `fape`: per-protein FAPE losses [B] of batch_loss(..., fape=...) (`-l fape`) or None."""
         from . import dp
         self.world = dp.world_size()
         self.n_res = n_res
@@ -249,7 +283,8 @@ class LossReport:
             B = 0 if stats is None else stats.shape[0]
             self._B = B
             n_lddt = 2 * B if lddt is not None else 0
-            n = B * 8 + 6 + 1 + B + n_lddt + (B if slddt is not None else 0)
+            n_slddt = B if slddt is not None else 0
+            n = B * 8 + 6 + 1 + B + n_lddt + n_slddt + (B if fape is not None else 0)
             buf = _pinned("report32", n, torch.float32, device)
             if stats is not None:
                 buf[:B * 8].copy_(stats.reshape(-1), non_blocking=True)
@@ -262,14 +297,16 @@ class LossReport:
             if lddt is not None:
                 buf[B * 9 + 7:B * 9 + 7 + n_lddt].copy_(lddt.reshape(-1), non_blocking=True)
             if slddt is not None:
-                buf[B * 9 + 7 + n_lddt:].copy_(slddt.reshape(-1), non_blocking=True)
-            self._has_slddt, self._n_lddt = slddt is not None, n_lddt
+                buf[B * 9 + 7 + n_lddt:B * 9 + 7 + n_lddt + n_slddt].copy_(slddt.reshape(-1), non_blocking=True)
+            if fape is not None:
+                buf[B * 9 + 7 + n_lddt + n_slddt:].copy_(fape.reshape(-1), non_blocking=True)
+            self._has_slddt, self._n_lddt, self._n_slddt, self._has_fape = slddt is not None, n_lddt, n_slddt, fape is not None
             self._has = (stats is not None, mse_sums_local is not None, status is not None, rmsd is not None)
             self._has_lddt = lddt is not None
             self._buf = buf
             self.global_mse_sums = mse_sums_local
         else:
-            v = torch.zeros(self._NVEC, dtype=torch.float64, device=device)
+            v = torch.zeros(self._NVEC + self._NFAPE, dtype=torch.float64, device=device)
             if stats is not None:
                 v[0:4] = stats[:, :4].double().sum(0)
                 v[4] = stats.shape[0]
@@ -289,10 +326,15 @@ class LossReport:
                 ok = torch.isfinite(slddt)
                 v[23] = torch.where(ok, slddt, torch.zeros_like(slddt)).double().sum()
                 v[24] = ok.sum()
+            if fape is not None:
+                ok = torch.isfinite(fape)
+                v[25] = torch.where(ok, fape, torch.zeros_like(fape)).double().sum()
+                v[26] = ok.sum()
             self._has_slddt = slddt is not None       # (a rank with an empty shard passes None and reads the global value)
+            self._has_fape = fape is not None
             dp.all_reduce_sum_(v)
             self.global_mse_sums = v[6:12].float()
-            buf = _pinned("report64", self._NVEC, torch.float64, device)
+            buf = _pinned("report64", self._NVEC + self._NFAPE, torch.float64, device)
             buf.copy_(v, non_blocking=True)
             self._buf = buf
         self._event = torch.cuda.Event()
@@ -302,7 +344,7 @@ class LossReport:
         """Block until the copies have landed; returns a dict of host numbers (float64 / int)."""
         self._event.synchronize()
         out = {"drmsd": 0.0, "lndrmsd": 0.0, "drmsd-bb": 0.0, "lndrmsd-bb": 0.0, "rmsd": None, "n_proteins": 0,
-               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None, "slddt": None}
+               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None, "slddt": None, "fape": None}
         if self.world == 1:
             B = self._B
             host = self._buf.numpy()
@@ -323,9 +365,13 @@ class LossReport:
                     ok = np.isfinite(sc[:, k])
                     out[name] = float(sc[ok, k].mean()) if ok.any() else float("nan")
             if self._has_slddt:                                      # mean over the proteins with a score
-                sl = host[B * 9 + 7 + self._n_lddt:].astype(np.float64)
+                sl = host[B * 9 + 7 + self._n_lddt:B * 9 + 7 + self._n_lddt + self._n_slddt].astype(np.float64)
                 ok = np.isfinite(sl)
                 out["slddt"] = float(sl[ok].mean()) if ok.any() else float("nan")
+            if self._has_fape:                                       # mean over the proteins with a finite loss
+                fa = host[B * 9 + 7 + self._n_lddt + self._n_slddt:].astype(np.float64)
+                ok = np.isfinite(fa)
+                out["fape"] = float(fa[ok].mean()) if ok.any() else float("nan")
         else:
             v = self._buf.numpy().copy()
             n = max(v[4], 1.0)
@@ -339,6 +385,8 @@ class LossReport:
             out["lddt-ca"] = v[20] / v[22] if v[22] > 0 else float("nan")
             if v[24] > 0 or self._has_slddt:
                 out["slddt"] = v[23] / v[24] if v[24] > 0 else float("nan")
+            if v[26] > 0 or self._has_fape:
+                out["fape"] = v[25] / v[26] if v[26] > 0 else float("nan")
         return out
 
 

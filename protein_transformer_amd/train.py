@@ -124,22 +124,34 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     losses over the proteins of the GLOBAL batch that have one.  The ten reference keys keep their meaning: the dRMSD statistics
     are taken forward-only on the coordinates already built.  In `eval_mode` the loss is computed forward-only on the coordinates
     evaluation has built.  Under any other `-l` nothing is computed and the key is absent.
+
+    `-l fape` (no counterpart in the reference): the structure is trained on the frame aligned point error of csrc/fape.hip
+    (`--fape_clamp`; definition in include/ptamd.h) - the one loss here that tells a structure from its mirror image.  Everything
+    said of `-l slddt` holds with `fape-full` as the new key: the injected gradient is d(sum_i fape_i), `loss` = `fape-full` is
+    the mean over the proteins of the GLOBAL batch that have a finite loss, the ten reference keys keep their meaning, `eval_mode`
+    is forward-only on the coordinates evaluation has built, and under any other `-l` nothing is computed and the key is absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
     slddt = (float(getattr(args, "slddt_cutoff", 15.0)), float(getattr(args, "slddt_temperature", 1.0))) if args.loss == "slddt" else None
-    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined", "slddt"] or eval_mode
+    fape = float(getattr(args, "fape_clamp", 10.0)) if args.loss == "fape" else None
+    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined", "slddt", "fape"] or eval_mode
     backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
     if slddt is not None and backbone:
         raise ValueError(SLDDT_BACKBONE_MESSAGE)
+    if fape is not None and backbone:
+        raise ValueError(FAPE_BACKBONE_MESSAGE)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
-    sums = stats = grad = status = rmsd = lddt = sl = None
+    sums = stats = grad = status = rmsd = lddt = sl = fa = None
     if not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
             if slddt is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the smooth lDDT
                 stats, grad, status, crd, sl = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
                                                           slddt=slddt)
+            elif fape is not None:     # the same with the frame aligned point error
+                stats, grad, status, crd, fa = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
+                                                          fape=fape)
             elif backbone and not eval_mode:
                 stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
                 crd = None
@@ -159,7 +171,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
                 from .eval_metrics import lddt_batch
                 lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
-    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt, slddt=sl)
+    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt, slddt=sl,
+                        fape=fa)
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -185,6 +198,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             loss = d_bb_loss if backbone else d_loss
         elif args.loss == "slddt":
             loss = np.float64(host["slddt"] if host["slddt"] is not None else float("nan"))
+        elif args.loss == "fape":
+            loss = np.float64(host["fape"] if host["fape"] is not None else float("nan"))
         elif args.loss == "combined":
             # (a training step under the flag: ln_d_loss IS the backbone value; only evaluation has two different numbers)
             loss = combine_drmsd_mse(d_bb_ln_loss, m_loss_full, w=args.combined_drmsd_weight, log=False) \
@@ -199,6 +214,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
     if slddt is not None:
         out["slddt-full"] = loss
+    if fape is not None:
+        out["fape-full"] = loss
     if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
         nan = float("nan")
         out["lddt-full"] = np.float64(host["lddt"] if host["lddt"] is not None else nan)
@@ -486,6 +503,10 @@ SLDDT_BACKBONE_MESSAGE = ("-l slddt is an all-atom loss: it cannot be combined w
                           "(a backbone or C-alpha smooth lDDT does not exist here)")
 
 
+FAPE_BACKBONE_MESSAGE = ("-l fape needs every atom: it cannot be combined with --backbone_loss "
+                         "(a backbone FAPE needs the compact backbone layout and does not exist here)")
+
+
 class _Parser(argparse.ArgumentParser):
     """Refuses, at argument parsing, the combinations of flags that no code path serves."""
 
@@ -496,12 +517,16 @@ class _Parser(argparse.ArgumentParser):
         if a.loss == "slddt" and not (a.slddt_cutoff > 0 and np.isfinite(a.slddt_cutoff)
                                       and a.slddt_temperature > 0 and np.isfinite(a.slddt_temperature)):
             self.error("--slddt_cutoff and --slddt_temperature must be finite and positive")
+        if a.loss == "fape" and a.backbone_loss:
+            self.error(FAPE_BACKBONE_MESSAGE)
+        if a.loss == "fape" and not a.fape_clamp > 0:          # (NaN fails; inf = unclamped)
+            self.error("--fape_clamp must be positive (inf = unclamped)")
         return a
 
 
 def early_stopping_target(args):
     """(es_mode, es_metric) of train.py:567: `-esm <train|test|valid-NN>-<loss name>`, by default the training loss of the run.
-    (Loss names carry no hyphen - `slddt` - because of this split.)"""
+    (Loss names carry no hyphen - `slddt`, `fape` - because of this split.)"""
     return tuple((args.early_stopping_metric or f"train-{args.loss}").rsplit("-", 1))
 
 
@@ -522,8 +547,9 @@ def create_parser():
     training.add_argument('-es', '--early_stopping', type=int, default=20)
     training.add_argument('-nws', '--n_warmup_steps', type=int, default=10_000)
     training.add_argument('-cg', '--clip', type=float, default=1)
-    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", "slddt"], default="combined",
-                          help="slddt (not in the reference): the smooth lDDT loss of AlphaFold 3 over all atoms")
+    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", "slddt", "fape"], default="combined",
+                          help="slddt (not in the reference): the smooth lDDT loss of AlphaFold 3 over all atoms; fape (not in "
+                               "the reference): the frame aligned point error of AlphaFold 2, backbone frames x all atoms")
     training.add_argument('--train_only', action='store_true')
     training.add_argument('--lr_scheduling', type=str, choices=['noam', 'plateau'], default='plateau')
     training.add_argument('--patience', type=int, default=10)
@@ -590,6 +616,8 @@ def create_parser():
                      help="-l slddt: inclusion radius of the smooth lDDT loss in the TRUE structure, in Angstrom.")
     new.add_argument("--slddt_temperature", type=float, default=1.0,
                      help="-l slddt: temperature of the four sigmoids (1 = AlphaFold 3; smaller approaches the hard lDDT).")
+    new.add_argument("--fape_clamp", type=float, default=10.0,
+                     help="-l fape: the clamp of the frame aligned point error, in Angstrom (inf = unclamped).")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
