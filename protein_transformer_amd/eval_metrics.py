@@ -49,13 +49,6 @@ def lddt_batch(pred_crd, true_crd, seq, cutoff=15.0):
     return score, per_res, counts
 
 
-def lddt_sums(score):
-    """score [B,2] -> device fp64 [4] = (sum of the finite lddt-full, sum of the finite lddt-ca, their two counts): what
-    losses.LossReport carries, so that the mean over the proteins WITH a score can be formed over a global batch."""
-    ok = torch.isfinite(score)
-    return torch.cat([torch.where(ok, score, torch.zeros_like(score)).double().sum(0), ok.double().sum(0)])
-
-
 def rmsd(a, b):
     """RMSD between two [n,3] coordinate sets after superposing `a` on `b` (losses.py:281-286); host float."""
     dev = a.device if torch.is_tensor(a) and a.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -82,10 +75,10 @@ def batch_rmsd(pred_sincos, true_crds, input_seqs):
 def batch_lddt(pred_sincos, true_crds, input_seqs, cutoff=15.0):
     """(lddt-full, lddt-ca): means over the proteins with a finite score of the lDDT of the structures built from
     pred_sincos (NaN when no protein has one); one host read."""
-    from .losses import angles_forward
+    from .losses import angles_forward, finite_sums
     from .protein.Structure import nerf_forward
     B, L = input_seqs.shape
     ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
     crd, _ = nerf_forward(ang, input_seqs)
-    s = lddt_sums(lddt_batch(crd, true_crds, input_seqs, cutoff)[0]).cpu().numpy()
+    s = finite_sums(lddt_batch(crd, true_crds, input_seqs, cutoff)[0]).cpu().numpy()
     return tuple(float(s[k] / s[2 + k]) if s[2 + k] > 0 else float("nan") for k in range(2))

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import dp
 from .dataset import VALID_SPLITS
+from .losses import EXTRA_LOSSES
 from .protein.Sequence import VOCAB
 
 _TRACKED = ("drmsd-full", "lndrmsd-full", "mse-full", "combined-full", "rmsd-full", "drmsd-bb", "lndrmsd-bb",
@@ -25,7 +26,7 @@ _LDDT = ("lddt-full", "lddt-ca")
 # `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
 # above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
 # exactly their keys
-_EXTRA_LOSSES = ("slddt", "fape")
+_EXTRA_LOSSES = tuple(EXTRA_LOSSES)
 
 
 class EarlyStoppingCondition(Exception):

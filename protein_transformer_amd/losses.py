@@ -6,10 +6,13 @@ drmsd_work :49, angles_to_coords :101, compute_batch_drmsd :133, mse_over_angles
 the arithmetic runs in csrc/geometry.hip and csrc/drmsd.hip through libptamd.  Nothing is moved
 to the CPU and no worker pool is needed: `device` and `pool` are accepted and ignored.
 """
+import functools
+from collections import namedtuple
+
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, dp
 from .protein.Sequence import VOCAB
 from .protein.structure_utils import get_backbone_from_full_coords  # noqa: F401  (losses.py:12: importable from here too)
 from .protein.Structure import (NUM_BB_ATOMS, NUM_PREDICTED_ANGLES, NUM_PREDICTED_COORDS, SC_ANGLES_START_POS, generate_coords,
@@ -128,6 +131,35 @@ def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
     return stats, npairs, nclamped, dcrd
 
 
+# ----------------------------------------------------------------------------- the extra structural losses
+# All the host code knows about a structural loss beside the dRMSD family (`train.py -l <name>`; the name is also its keyword in
+# `batch_loss` and `LossReport` and its key in `LossReport.wait()`).  run(crd, true_crds, seq, need_grad, params) -> (per-protein
+# loss [B], its gradient d/d(crd) or None); params(args): as batch_loss takes them; check(params): the parser's complaint or None.
+ExtraLoss = namedtuple("ExtraLoss", "name run params check backbone_message")
+
+
+def _run_slddt(crd, true_crds, seq, need_grad, params):
+    stats, _, dcrd = slddt_forward_backward(crd, true_crds, seq, need_grad=need_grad, cutoff=params[0], temperature=params[1])
+    return stats[:, 0], dcrd
+
+
+def _run_fape(crd, true_crds, seq, need_grad, params):
+    stats, _, _, dcrd = fape_forward_backward(crd, true_crds, seq, need_grad=need_grad, clamp=params)
+    return stats[:, 0], dcrd
+
+
+EXTRA_LOSSES = {e.name: e for e in (
+    ExtraLoss("slddt", _run_slddt, lambda a: (float(getattr(a, "slddt_cutoff", 15.0)), float(getattr(a, "slddt_temperature", 1.0))),
+              lambda p: None if all(0 < x < np.inf for x in p) else "--slddt_cutoff and --slddt_temperature must be finite and positive",
+              "-l slddt is an all-atom loss: it cannot be combined with --backbone_loss "
+              "(a backbone or C-alpha smooth lDDT does not exist here)"),
+    ExtraLoss("fape", _run_fape, lambda a: float(getattr(a, "fape_clamp", 10.0)),
+              lambda p: None if p > 0 else "--fape_clamp must be positive (inf = unclamped)",          # (NaN fails)
+              "-l fape needs every atom: it cannot be combined with --backbone_loss "
+              "(a backbone FAPE needs the compact backbone layout and does not exist here)"),
+)}
+
+
 class _DrmsdFn(torch.autograd.Function):
     """drmsd(a, b) for two [n,3] point sets, differentiable in a."""
 
@@ -197,42 +229,32 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     [:, 4]) are the backbone numbers of the full call, the gradient is d(sum_i lndrmsd-bb_i)/d(pred_sincos) - exactly zero in the
     side-chain channels - and the coordinates of `return_crd` are the compact [B, L*3, 3] backbone.
 
-    `slddt` = (cutoff, temperature) (`train.py -l slddt`; None: everything above is unchanged): the structure is trained on the
-    smooth lDDT loss instead - angles -> NeRF forward -> smooth lDDT -> NeRF adjoint -> angles adjoint.  The gradient is
-    d(sum_i slddt_i)/d(pred_sincos), `stats` are still the dRMSD statistics (taken forward-only on the same coordinates, so logs
-    stay comparable between runs), and the per-protein smooth-lDDT losses [B] (NaN for a protein without an included pair) are
-    appended to the returned tuple as its last value.
-
-    `fape` = clamp in Angstrom (`train.py -l fape`; None: everything above is unchanged): the same path with the frame aligned
-    point error of csrc/fape.hip in the place of the smooth lDDT - the gradient is d(sum_i fape_i)/d(pred_sincos), `stats` the
-    forward-only dRMSD statistics, and the per-protein FAPE losses [B] (NaN for a protein without a frame) are appended last.
+    An extra loss (EXTRA_LOSSES: one keyword each, at most one given; None: everything above is unchanged): the structure is
+    trained on that loss instead - angles -> NeRF forward -> the loss -> NeRF adjoint -> angles adjoint.  The gradient is
+    d(sum_i loss_i)/d(pred_sincos), `stats` are still the dRMSD statistics (taken forward-only on the same coordinates, so logs stay
+    comparable between runs), and the per-protein losses [B] (NaN for a protein without one) are appended as the last value.
+      `slddt` = (cutoff, temperature): the smooth lDDT loss of csrc/slddt.hip (`train.py -l slddt`).
+      `fape` = clamp in Angstrom: the frame aligned point error of csrc/fape.hip (`train.py -l fape`).
     """
-    assert slddt is None or fape is None, "one structural loss at a time"
-    if slddt is not None:
-        assert not backbone_only, "the smooth lDDT loss is an all-atom loss"
-    if fape is not None:
-        assert not backbone_only, "FAPE needs every atom (a backbone FAPE does not exist here)"
+    given = [(EXTRA_LOSSES[name], params) for name, params in (("slddt", slddt), ("fape", fape)) if params is not None]
+    assert len(given) <= 1, "one structural loss at a time"
+    extra, params = given[0] if given else (None, None)
+    assert extra is None or not backbone_only, extra.backbone_message
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
     crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
-    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs,
-                                         need_grad=do_backward and slddt is None and fape is None, backbone_only=backbone_only)
-    sl = None
-    if slddt is not None:
-        sl_stats, _, dcrd = slddt_forward_backward(crd, true_crds, input_seqs, need_grad=do_backward, cutoff=slddt[0],
-                                                   temperature=slddt[1])
-        sl = sl_stats[:, 0]
-    if fape is not None:
-        fa_stats, _, _, dcrd = fape_forward_backward(crd, true_crds, input_seqs, need_grad=do_backward, clamp=fape)
-        sl = fa_stats[:, 0]
+    stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward and extra is None,
+                                         backbone_only=backbone_only)
+    if extra is not None:
+        per_protein, dcrd = extra.run(crd, true_crds, input_seqs, do_backward, params)
     grad = None
     if do_backward:
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
     out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
-    return out if sl is None else out + (sl,)
+    return out if extra is None else out + (per_protein,)
 
 
 # ----------------------------------------------------------------------------- statistics hand-over
@@ -247,6 +269,122 @@ def _pinned(kind, n, dtype, device):
     if buf is None:
         buf = _PINNED[key] = torch.empty(n, dtype=dtype).pin_memory()
     return buf
+
+
+# A CHANNEL of a report: per-protein fp32 values [B], reported as their mean over the proteins of the global batch that have a
+# finite one.  A field of k columns carries k channels (`lddt`, of --eval_lddt: two); field -> the `wait()` keys of its columns:
+_CHANNEL_FIELDS = {"lddt": ("lddt", "lddt-ca"), **{name: (name,) for name in EXTRA_LOSSES}}
+_MEANS = ("drmsd", "lndrmsd", "drmsd-bb", "lndrmsd-bb")        # stats[:, :4], reported as their means over the proteins
+_NO_REPORT = {**dict.fromkeys(_MEANS, 0.0), "rmsd": None, "n_proteins": 0, "status": 0, "n_res": None, "mse": None,
+              **{key: None for keys in _CHANNEL_FIELDS.values() for key in keys}}
+
+
+def _take(fields):
+    """[(name, width), ...] -> ({name: slice}, total width): consecutive fields behind one running cursor (what atom_tiles::take
+    does for the kernels' workspaces).  Every offset of a report comes from here."""
+    at, cursor = {}, 0
+    for name, width in fields:
+        at[name] = slice(cursor, cursor + width)
+        cursor += width
+    return at, cursor
+
+
+def finite_sums(x):
+    """x [B] or [B,k] -> fp64 [2k] on x's device: per column the sum of the finite entries, then their counts.  No host sync."""
+    ok = torch.isfinite(x)
+    return torch.cat([torch.where(ok, x, torch.zeros_like(x)).double().sum(0).reshape(-1), ok.double().sum(0).reshape(-1)])
+
+
+def finite_mean(x):
+    """The mean, in fp64, of the finite entries of a host array; NaN when it has none."""
+    x = np.asarray(x).astype(np.float64)
+    return float(x[np.isfinite(x)].mean()) if np.isfinite(x).any() else float("nan")
+
+
+@functools.lru_cache(maxsize=None)
+def _local_layout(B, present):
+    """({field of `present`: its slice}, size): stats, mse, status, rmsd keep their room when absent, a channel field takes none."""
+    at, size = _take([("stats", 8 * B), ("mse", 6), ("status", 1), ("rmsd", B)]
+                     + [(field, len(keys) * B) for field, keys in _CHANNEL_FIELDS.items() if field in present])
+    return {name: at[name] for name in present}, size
+
+
+def pack_local(stats=None, mse=None, status=None, rmsd=None, channels=None, alloc=torch.empty):
+    """What a single process reports, in one fp32 buffer: stats [B,8], the six MSE sums, the status word (int32[1], as raw bits),
+    rmsd [B] and the `channels` ({field of _CHANNEL_FIELDS: [B] or [B,k]}), each of them or None.  One (asynchronous) copy per
+    field into `alloc(size)` (default: a host tensor); returns the buffer and its layout (B, {field that was passed: slice})."""
+    given = {k: t for k, t in dict(stats=stats, mse=mse, status=status, rmsd=rmsd, **(channels or {})).items() if t is not None}
+    B = next((t.shape[0] for name, t in given.items() if name not in ("mse", "status")), 0)
+    at, size = _local_layout(B, tuple(given))
+    buf = alloc(size)
+    for name, t in given.items():
+        dst = buf.view(torch.int32) if name == "status" else buf
+        dst[at[name]].copy_(t if t.dim() == 1 else t.reshape(-1), non_blocking=True)
+    return buf, (B, at)
+
+
+def unpack_local(host, layout, n_res=None):
+    """The `LossReport.wait()` dictionary of a single process, from the landed buffer (numpy fp32) and its layout: np.mean in fp64
+    over the proteins of the per-protein values; a channel over the proteins with a finite value."""
+    host, (B, at) = np.asarray(host), layout
+    out = dict(_NO_REPORT, n_res=n_res)
+    if "stats" in at and B:
+        st = host[at["stats"]].reshape(B, 8).astype(np.float64)
+        out.update({key: np.mean(st[:, k]) for k, key in enumerate(_MEANS)}, n_proteins=B)
+    if "mse" in at:
+        out["mse"] = host[at["mse"]].astype(np.float64)
+    if "status" in at:
+        out["status"] = int(host[at["status"]].view(np.int32)[0])
+    if "rmsd" in at and B:
+        out["rmsd"] = float(np.mean(host[at["rmsd"]].astype(np.float64)))
+    for field, keys in _CHANNEL_FIELDS.items():
+        if field in at:
+            values = host[at[field]].reshape(B, len(keys))
+            out.update({key: finite_mean(values[:, k]) for k, key in enumerate(keys)})
+    return out
+
+
+# The fp64 vector a rank adds to the SUM reduction.  sums: of stats[:, :4]; ranks_counted: the ranks that passed a residue count
+# (0: n_res stays None like on one rank); a channel field: its `finite_sums` (zeros on a rank that does not report it).
+VECTOR_SLOTS, VECTOR_SIZE = _take([("sums", 4), ("proteins", 1), ("rmsd_sum", 1), ("mse", 6), ("status_bits", 4), ("residues", 1),
+                                   ("rmsd_proteins", 1), ("ranks_counted", 1)]
+                                  + [(field, 2 * len(keys)) for field, keys in _CHANNEL_FIELDS.items()])
+
+
+def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, channels=None, device=None):
+    """This rank's vector of VECTOR_SLOTS (arguments as `pack_local`; an empty shard passes None for everything).  No host sync."""
+    S = VECTOR_SLOTS
+    v = torch.zeros(VECTOR_SIZE, dtype=torch.float64, device=device)
+    if stats is not None:
+        v[S["sums"]], v[S["proteins"]] = stats[:, :4].double().sum(0), stats.shape[0]
+    if rmsd is not None:
+        v[S["rmsd_sum"]], v[S["rmsd_proteins"]] = rmsd.double().sum(), rmsd.shape[0]
+    if mse is not None:
+        v[S["mse"]] = mse.double()
+    if status is not None:
+        v[S["status_bits"]] = ((status.to(torch.int64) >> torch.arange(4, device=status.device)) & 1).double()
+    v[S["residues"]], v[S["ranks_counted"]] = float(n_res or 0), 0.0 if n_res is None else 1.0
+    for field, t in (channels or {}).items():
+        if t is not None:
+            v[S[field]] = finite_sums(t)
+    return v
+
+
+def unpack_global(v, passed=()):
+    """The `LossReport.wait()` dictionary from the REDUCED vector (numpy fp64), the same on every rank.  A channel stays None unless
+    a protein of the global batch has a value (a rank with an empty shard reads it too) or this rank `passed` its field (then NaN)."""
+    one = {name: v[at][0] for name, at in VECTOR_SLOTS.items()}          # (the first entry of every slot: for the one-entry slots)
+    out = dict(_NO_REPORT, n_proteins=int(one["proteins"]), mse=v[VECTOR_SLOTS["mse"]],
+               status=sum(1 << k for k, n in enumerate(v[VECTOR_SLOTS["status_bits"]]) if n > 0),
+               n_res=int(one["residues"]) if one["ranks_counted"] > 0 else None)
+    out.update(zip(_MEANS, v[VECTOR_SLOTS["sums"]] / max(one["proteins"], 1.0)))
+    if one["rmsd_proteins"] > 0:
+        out["rmsd"] = one["rmsd_sum"] / one["rmsd_proteins"]
+    for field, keys in _CHANNEL_FIELDS.items():
+        total, count = v[VECTOR_SLOTS[field]].reshape(2, -1)
+        out.update({key: total[k] / count[k] if count[k] > 0 else float("nan")
+                    for k, key in enumerate(keys) if count[k] > 0 or field in passed})
+    return out
 
 
 class LossReport:
@@ -264,141 +402,29 @@ class LossReport:
     A rank whose shard is empty passes None for everything and still takes part in the reduction.
     """
 
-    # [0:4] sums of drmsd, ln, bb, bb-ln  [4] proteins  [5] sum rmsd  [6:12] mse sums  [12:16] status bits  [16] residues
-    # [17] proteins with rmsd  [18] ranks that passed a residue count (0: nobody counted - n_res stays None like on one rank)
-    # [19:21] sums of the finite lddt-full, lddt-ca  [21:23] proteins with a finite lddt-full, lddt-ca (--eval_lddt; else 0)
-    # [23] sum of the finite smooth-lDDT losses  [24] proteins with one (-l slddt; else 0)
-    _NVEC = 25
-    # behind them: [25] sum of the finite FAPE losses  [26] proteins with one (-l fape; else 0)
-    _NFAPE = 2
-
     def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
-        `slddt`: per-protein smooth-lDDT losses [B] of batch_loss(..., slddt=...) (`-l slddt`) or None.
-        `fape`: per-protein FAPE losses [B] of batch_loss(..., fape=...) (`-l fape`) or None."""
-        from . import dp
-        self.world = dp.world_size()
-        self.n_res = n_res
+        `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None."""
+        self.world, self.n_res = dp.world_size(), n_res
+        channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
         if self.world == 1:
-            B = 0 if stats is None else stats.shape[0]
-            self._B = B
-            n_lddt = 2 * B if lddt is not None else 0
-            n_slddt = B if slddt is not None else 0
-            n = B * 8 + 6 + 1 + B + n_lddt + n_slddt + (B if fape is not None else 0)
-            buf = _pinned("report32", n, torch.float32, device)
-            if stats is not None:
-                buf[:B * 8].copy_(stats.reshape(-1), non_blocking=True)
-            if mse_sums_local is not None:
-                buf[B * 8:B * 8 + 6].copy_(mse_sums_local, non_blocking=True)
-            if status is not None:       # raw int32 bits into the float slot
-                buf.view(torch.int32)[B * 8 + 6:B * 8 + 7].copy_(status, non_blocking=True)
-            if rmsd is not None:
-                buf[B * 8 + 7:B * 9 + 7].copy_(rmsd, non_blocking=True)
-            if lddt is not None:
-                buf[B * 9 + 7:B * 9 + 7 + n_lddt].copy_(lddt.reshape(-1), non_blocking=True)
-            if slddt is not None:
-                buf[B * 9 + 7 + n_lddt:B * 9 + 7 + n_lddt + n_slddt].copy_(slddt.reshape(-1), non_blocking=True)
-            if fape is not None:
-                buf[B * 9 + 7 + n_lddt + n_slddt:].copy_(fape.reshape(-1), non_blocking=True)
-            self._has_slddt, self._n_lddt, self._n_slddt, self._has_fape = slddt is not None, n_lddt, n_slddt, fape is not None
-            self._has = (stats is not None, mse_sums_local is not None, status is not None, rmsd is not None)
-            self._has_lddt = lddt is not None
-            self._buf = buf
+            buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
+                                     alloc=lambda n: _pinned("report32", n, torch.float32, device))
             self.global_mse_sums = mse_sums_local
+            self._unpack = lambda: unpack_local(buf.numpy(), layout, n_res)
         else:
-            v = torch.zeros(self._NVEC + self._NFAPE, dtype=torch.float64, device=device)
-            if stats is not None:
-                v[0:4] = stats[:, :4].double().sum(0)
-                v[4] = stats.shape[0]
-            if rmsd is not None:
-                v[5] = rmsd.double().sum()
-                v[17] = rmsd.shape[0]
-            if mse_sums_local is not None:
-                v[6:12] = mse_sums_local.double()
-            if status is not None:
-                v[12:16] = ((status.to(torch.int64) >> torch.arange(4, device=device)) & 1).double()
-            v[16] = float(n_res or 0)
-            v[18] = 0.0 if n_res is None else 1.0
-            if lddt is not None:
-                from .eval_metrics import lddt_sums
-                v[19:23] = lddt_sums(lddt)
-            if slddt is not None:
-                ok = torch.isfinite(slddt)
-                v[23] = torch.where(ok, slddt, torch.zeros_like(slddt)).double().sum()
-                v[24] = ok.sum()
-            if fape is not None:
-                ok = torch.isfinite(fape)
-                v[25] = torch.where(ok, fape, torch.zeros_like(fape)).double().sum()
-                v[26] = ok.sum()
-            self._has_slddt = slddt is not None       # (a rank with an empty shard passes None and reads the global value)
-            self._has_fape = fape is not None
-            dp.all_reduce_sum_(v)
-            self.global_mse_sums = v[6:12].float()
-            buf = _pinned("report64", self._NVEC + self._NFAPE, torch.float64, device)
+            v = dp.all_reduce_sum_(reduce_vector(stats, mse_sums_local, status, rmsd, n_res, channels, device))
+            self.global_mse_sums = v[VECTOR_SLOTS["mse"]].float()
+            buf = _pinned("report64", VECTOR_SIZE, torch.float64, device)
             buf.copy_(v, non_blocking=True)
-            self._buf = buf
+            self._unpack = lambda: unpack_global(buf.numpy().copy(), {field for field, t in channels.items() if t is not None})
         self._event = torch.cuda.Event()
         self._event.record()
 
     def wait(self):
         """Block until the copies have landed; returns a dict of host numbers (float64 / int)."""
         self._event.synchronize()
-        out = {"drmsd": 0.0, "lndrmsd": 0.0, "drmsd-bb": 0.0, "lndrmsd-bb": 0.0, "rmsd": None, "n_proteins": 0,
-               "status": 0, "n_res": self.n_res, "mse": None, "lddt": None, "lddt-ca": None, "slddt": None, "fape": None}
-        if self.world == 1:
-            B = self._B
-            host = self._buf.numpy()
-            has_stats, has_mse, has_status, has_rmsd = self._has
-            if has_stats and B:
-                st = host[:B * 8].reshape(B, 8).astype(np.float64)
-                out.update({"drmsd": np.mean(st[:, 0]), "lndrmsd": np.mean(st[:, 1]), "drmsd-bb": np.mean(st[:, 2]),
-                            "lndrmsd-bb": np.mean(st[:, 3]), "n_proteins": B})
-            if has_mse:
-                out["mse"] = host[B * 8:B * 8 + 6].astype(np.float64)
-            if has_status:
-                out["status"] = int(host[B * 8 + 6:B * 8 + 7].view(np.int32)[0])
-            if has_rmsd and B:
-                out["rmsd"] = float(np.mean(host[B * 8 + 7:B * 9 + 7].astype(np.float64)))
-            if self._has_lddt:
-                sc = host[B * 9 + 7:B * 9 + 7 + self._n_lddt].reshape(B, 2).astype(np.float64)
-                for k, name in enumerate(("lddt", "lddt-ca")):       # mean over the proteins with a score
-                    ok = np.isfinite(sc[:, k])
-                    out[name] = float(sc[ok, k].mean()) if ok.any() else float("nan")
-            if self._has_slddt:                                      # mean over the proteins with a score
-                sl = host[B * 9 + 7 + self._n_lddt:B * 9 + 7 + self._n_lddt + self._n_slddt].astype(np.float64)
-                ok = np.isfinite(sl)
-                out["slddt"] = float(sl[ok].mean()) if ok.any() else float("nan")
-            if self._has_fape:                                       # mean over the proteins with a finite loss
-                fa = host[B * 9 + 7 + self._n_lddt + self._n_slddt:].astype(np.float64)
-                ok = np.isfinite(fa)
-                out["fape"] = float(fa[ok].mean()) if ok.any() else float("nan")
-        else:
-            v = self._buf.numpy().copy()
-            n = max(v[4], 1.0)
-            out.update({"drmsd": v[0] / n, "lndrmsd": v[1] / n, "drmsd-bb": v[2] / n, "lndrmsd-bb": v[3] / n,
-                        "n_proteins": int(v[4]), "mse": v[6:12],
-                        "status": sum((1 << k) for k in range(4) if v[12 + k] > 0),
-                        "n_res": int(v[16]) if v[18] > 0 else None})
-            if v[17] > 0:
-                out["rmsd"] = v[5] / v[17]
-            out["lddt"] = v[19] / v[21] if v[21] > 0 else float("nan")
-            out["lddt-ca"] = v[20] / v[22] if v[22] > 0 else float("nan")
-            if v[24] > 0 or self._has_slddt:
-                out["slddt"] = v[23] / v[24] if v[24] > 0 else float("nan")
-            if v[26] > 0 or self._has_fape:
-                out["fape"] = v[25] / v[26] if v[26] > 0 else float("nan")
-        return out
-
-
-def _stats_to_host(stats, status):
-    """Back-compatible helper: (pinned buffer of B*8 + 1 floats, event recorded behind the copy)."""
-    n = stats.numel()
-    buf = _pinned("stats", n + 1, torch.float32, stats.device)
-    buf[:n].copy_(stats.reshape(-1), non_blocking=True)
-    buf[n:].copy_(status.float(), non_blocking=True)   # a handful of flag bits: exact in fp32
-    done = torch.cuda.Event()
-    done.record()
-    return buf, done
+        return self._unpack()
 
 
 def compute_batch_drmsd(pred_angs, true_crds, input_seqs, device=None, return_rmsd=False,

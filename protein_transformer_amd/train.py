@@ -28,7 +28,7 @@ from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
 from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging,
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
-from .losses import LossReport, batch_loss, combine_drmsd_mse, mse_grad, mse_sums
+from .losses import EXTRA_LOSSES, LossReport, batch_loss, combine_drmsd_mse, mse_grad, mse_sums
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
 from .optim import FusedAdam, FusedSGD, ScheduledOptim
@@ -118,40 +118,28 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     lDDT (eval_metrics.lddt_batch, on the coordinates built for the dRMSD and `rmsd-full`) over the proteins of the global batch
     that have a score.  Without the flag, and in every training step, nothing is computed and the keys are absent.
 
-    `-l slddt` (no counterpart in the reference): the structure is trained on the smooth lDDT loss of csrc/slddt.hip
-    (`--slddt_cutoff`, `--slddt_temperature`; definition in include/ptamd.h).  The injected gradient is d(sum_i slddt_i), the SUM
-    over proteins like every other structural loss here; `loss` and the new key `slddt-full` are the mean of the per-protein
-    losses over the proteins of the GLOBAL batch that have one.  The ten reference keys keep their meaning: the dRMSD statistics
-    are taken forward-only on the coordinates already built.  In `eval_mode` the loss is computed forward-only on the coordinates
-    evaluation has built.  Under any other `-l` nothing is computed and the key is absent.
-
-    `-l fape` (no counterpart in the reference): the structure is trained on the frame aligned point error of csrc/fape.hip
-    (`--fape_clamp`; definition in include/ptamd.h) - the one loss here that tells a structure from its mirror image.  Everything
-    said of `-l slddt` holds with `fape-full` as the new key: the injected gradient is d(sum_i fape_i), `loss` = `fape-full` is
-    the mean over the proteins of the GLOBAL batch that have a finite loss, the ten reference keys keep their meaning, `eval_mode`
-    is forward-only on the coordinates evaluation has built, and under any other `-l` nothing is computed and the key is absent.
+    `-l slddt`, `-l fape` (losses.EXTRA_LOSSES; not in the reference): the structure is trained on that loss.  The injected
+    gradient is d(sum_i loss_i), the SUM over proteins; `loss` and the new key `<name>-full` are the mean of the per-protein losses
+    over the proteins of the GLOBAL batch that have a finite one.  The ten reference keys keep their meaning: the dRMSD statistics
+    are taken forward-only on the coordinates already built, as is the loss itself in `eval_mode`.  Under any other `-l` no key.
+      slddt: the smooth lDDT loss of csrc/slddt.hip (`--slddt_cutoff`, `--slddt_temperature`; definition in include/ptamd.h).
+      fape: the frame aligned point error of csrc/fape.hip (`--fape_clamp`): it alone tells a structure from its mirror image.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
-    slddt = (float(getattr(args, "slddt_cutoff", 15.0)), float(getattr(args, "slddt_temperature", 1.0))) if args.loss == "slddt" else None
-    fape = float(getattr(args, "fape_clamp", 10.0)) if args.loss == "fape" else None
-    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined", "slddt", "fape"] or eval_mode
+    extra = EXTRA_LOSSES.get(args.loss)
+    need_drmsd = args.loss in ["lndrmsd", "drmsd", "combined"] or extra is not None or eval_mode
     backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
-    if slddt is not None and backbone:
-        raise ValueError(SLDDT_BACKBONE_MESSAGE)
-    if fape is not None and backbone:
-        raise ValueError(FAPE_BACKBONE_MESSAGE)
+    if extra is not None and backbone:
+        raise ValueError(extra.backbone_message)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
-    sums = stats = grad = status = rmsd = lddt = sl = fa = None
+    sums = stats = grad = status = rmsd = lddt = per_protein = None
     if not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
-            if slddt is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the smooth lDDT
-                stats, grad, status, crd, sl = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
-                                                          slddt=slddt)
-            elif fape is not None:     # the same with the frame aligned point error
-                stats, grad, status, crd, fa = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
-                                                          fape=fape)
+            if extra is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the extra loss
+                stats, grad, status, crd, per_protein = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
+                                                                   **{extra.name: extra.params(args)})
             elif backbone and not eval_mode:
                 stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
                 crd = None
@@ -171,8 +159,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
                 from .eval_metrics import lddt_batch
                 lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
-    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt, slddt=sl,
-                        fape=fa)
+    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
+                        **({extra.name: per_protein} if extra is not None else {}))
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -183,6 +171,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             g = grad
         pred.backward(gradient=g.view_as(pred))
     host = report.wait()
+    channel = lambda k: np.float64(float("nan") if host[k] is None else host[k])      # noqa: E731  (None: nobody reported it)
     if need_drmsd:
         raise_for_status(host["status"], theta_is_error=False)
     m = host["mse"] if host["mse"] is not None else np.full(6, np.nan)
@@ -196,10 +185,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             loss = d_bb_ln_loss if backbone else ln_d_loss
         elif args.loss == "drmsd":
             loss = d_bb_loss if backbone else d_loss
-        elif args.loss == "slddt":
-            loss = np.float64(host["slddt"] if host["slddt"] is not None else float("nan"))
-        elif args.loss == "fape":
-            loss = np.float64(host["fape"] if host["fape"] is not None else float("nan"))
+        elif extra is not None:
+            loss = channel(extra.name)
         elif args.loss == "combined":
             # (a training step under the flag: ln_d_loss IS the backbone value; only evaluation has two different numbers)
             loss = combine_drmsd_mse(d_bb_ln_loss, m_loss_full, w=args.combined_drmsd_weight, log=False) \
@@ -212,14 +199,10 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     out = {"loss": loss, "drmsd-full": d_loss, "lndrmsd-full": ln_d_loss, "drmsd-bb": d_bb_loss,
            "lndrmsd-bb": d_bb_ln_loss, "combined-full": c_loss, "mse-full": m_loss_full, "mse-bb": m_loss_bb,
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
-    if slddt is not None:
-        out["slddt-full"] = loss
-    if fape is not None:
-        out["fape-full"] = loss
+    if extra is not None:
+        out[f"{extra.name}-full"] = loss
     if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
-        nan = float("nan")
-        out["lddt-full"] = np.float64(host["lddt"] if host["lddt"] is not None else nan)
-        out["lddt-ca"] = np.float64(host["lddt-ca"] if host["lddt-ca"] is not None else nan)
+        out["lddt-full"], out["lddt-ca"] = channel("lddt"), channel("lddt-ca")
     if host["n_res"] is not None:
         out["n-residues"] = host["n_res"]                      # residues of the GLOBAL batch (speed meter, log.py)
     return out
@@ -499,12 +482,7 @@ def determine_largest_batch_size(args, data, device, angle_means, fraction_to_ke
     return max_batch_size
 
 
-SLDDT_BACKBONE_MESSAGE = ("-l slddt is an all-atom loss: it cannot be combined with --backbone_loss "
-                          "(a backbone or C-alpha smooth lDDT does not exist here)")
-
-
-FAPE_BACKBONE_MESSAGE = ("-l fape needs every atom: it cannot be combined with --backbone_loss "
-                         "(a backbone FAPE needs the compact backbone layout and does not exist here)")
+SLDDT_BACKBONE_MESSAGE, FAPE_BACKBONE_MESSAGE = (EXTRA_LOSSES[name].backbone_message for name in ("slddt", "fape"))
 
 
 class _Parser(argparse.ArgumentParser):
@@ -512,15 +490,10 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
-        if a.loss == "slddt" and a.backbone_loss:
-            self.error(SLDDT_BACKBONE_MESSAGE)
-        if a.loss == "slddt" and not (a.slddt_cutoff > 0 and np.isfinite(a.slddt_cutoff)
-                                      and a.slddt_temperature > 0 and np.isfinite(a.slddt_temperature)):
-            self.error("--slddt_cutoff and --slddt_temperature must be finite and positive")
-        if a.loss == "fape" and a.backbone_loss:
-            self.error(FAPE_BACKBONE_MESSAGE)
-        if a.loss == "fape" and not a.fape_clamp > 0:          # (NaN fails; inf = unclamped)
-            self.error("--fape_clamp must be positive (inf = unclamped)")
+        extra = EXTRA_LOSSES.get(a.loss)
+        problem = extra and (extra.backbone_message if a.backbone_loss else extra.check(extra.params(a)))
+        if problem:
+            self.error(problem)
         return a
 
 
@@ -547,7 +520,7 @@ def create_parser():
     training.add_argument('-es', '--early_stopping', type=int, default=20)
     training.add_argument('-nws', '--n_warmup_steps', type=int, default=10_000)
     training.add_argument('-cg', '--clip', type=float, default=1)
-    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", "slddt", "fape"], default="combined",
+    training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", *EXTRA_LOSSES], default="combined",
                           help="slddt (not in the reference): the smooth lDDT loss of AlphaFold 3 over all atoms; fape (not in "
                                "the reference): the frame aligned point error of AlphaFold 2, backbone frames x all atoms")
     training.add_argument('--train_only', action='store_true')

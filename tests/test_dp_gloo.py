@@ -16,16 +16,24 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _worker(rank, world, port, out_dir):
+def _join_gloo(rank, world, port):
+    """How every worker process of these tests starts: the torchrun environment, the repository on sys.path, one thread, the
+    gloo group joined.  Returns the dp module."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from oracle import encoder as oenc, losses as olosses
-    from protein_transformer_amd import dp, synthetic
+    from protein_transformer_amd import dp
     torch.set_num_threads(1)
     dp.init_from_env(backend="gloo")
     assert dp.world_size() == world and dp.rank() == rank
+    return dp
+
+
+def _worker(rank, world, port, out_dir):
+    dp = _join_gloo(rank, world, port)
+    from oracle import encoder as oenc, losses as olosses
+    from protein_transformer_amd import synthetic
     from oracle import geometry
     lens = [9, 7, 8, 6, 5]                       # 5 proteins over 2 ranks: shards of 3 and 2
     build = lambda ang, seq: torch.stack([                                     # noqa: E731
@@ -182,14 +190,9 @@ def _worker4(rank, world, port, out_dir):
     """world_size 4, shards of 2 / 1 / 1 / 0 proteins: every rank issues the same per-slice reductions in the same order
     (the rank with nothing walks the slice list with a zero buffer), the loss statistics come out as statistics of the
     global batch on every rank, and the comm meter counts the bytes it should."""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank))
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    dp = _join_gloo(rank, world, port)
     from oracle import encoder as oenc, geometry, losses as olosses
-    from protein_transformer_amd import dp, synthetic
-    torch.set_num_threads(1)
-    dp.init_from_env(backend="gloo")
+    from protein_transformer_amd import synthetic
     assert dp.world_size() == 4
     lens = [9, 7, 8, 6]
     build = lambda ang, seq: torch.stack([                                     # noqa: E731

@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_slddt import PAD, SLOTS, _chains, _make, cloud, present_atoms, rel_l2, stack
+from test_gpu_slddt import PAD, SLOTS, _chains, _dp_worker, _make, cloud, present_atoms, rel_l2, stack
 
 pytestmark = pytest.mark.gpu
 
@@ -464,3 +464,33 @@ def test_five_adam_steps_lower_the_loss():
     print("fape-full trace:", " ".join(f"{v:.5f}" for v in trace))
     assert np.isfinite(trace).all()
     assert trace[-1] < trace[0]
+
+
+# ----------------------------------------------------------------------------- 7. data parallel
+KEYS = ("loss", "fape-full", "drmsd-full", "lndrmsd-full", "drmsd-bb", "lndrmsd-bb", "mse-full")
+
+
+def test_two_ranks_reproduce_the_single_process_step(tmp_path):
+    """The twin of the test of this name in tests/test_gpu_slddt.py (its worker, its 3 + 2 split, its bars): the FAPE sum and count
+    travel in LossReport's vector, so every rank reports the mean over the GLOBAL batch."""
+    import torch.multiprocessing as mp
+
+    import test_gpu_dp as base
+    from protein_transformer_amd.train import train_step
+    mp.spawn(_dp_worker, args=(2, base._free_port(), str(tmp_path), "fape", KEYS), nprocs=2, join=True)
+    dev = torch.device("cuda:0")
+    model, opt, args, batch, lens = _make(dev, "fape")
+    # every protein of this batch has a frame (the two-residue one keeps N, CA, C of its first residue), so both shards report
+    assert all(len(frame_residues(t, s)) > 0 for t, s in zip(batch[2].numpy(), batch[0].numpy()))
+    start = model.flat_parameters()[0].cpu().numpy().copy()
+    losses = train_step(model, opt, args, *(t.to(dev) for t in batch))
+    full = model.flat_parameters()[0].cpu().numpy()
+    f0, f1 = np.load(tmp_path / "flat0.npy"), np.load(tmp_path / "flat1.npy")
+    assert np.array_equal(f0, f1)                                   # ranks stay in lock step
+    upd, upd_dp = full - start, f0 - start
+    assert np.linalg.norm(upd) > 0
+    assert np.linalg.norm(upd_dp - upd) <= 1e-4 * np.linalg.norm(upd)
+    l0, l1 = np.load(tmp_path / "loss0.npy"), np.load(tmp_path / "loss1.npy")
+    assert np.array_equal(l0, l1)                                   # every rank reports the GLOBAL statistics
+    assert l0 == pytest.approx(np.array([float(losses[k]) for k in KEYS]), rel=1e-5, abs=1e-7)
+    assert 0.0 < float(losses["loss"]) < 1.0

@@ -496,7 +496,9 @@ def test_thirty_adam_steps_lower_the_loss():
 KEYS = ("loss", "slddt-full", "drmsd-full", "lndrmsd-full", "drmsd-bb", "lndrmsd-bb", "mse-full")
 
 
-def _dp_worker(rank, world, port, out_dir):
+def _dp_worker(rank, world, port, out_dir, loss="slddt", keys=KEYS):
+    """One rank of a two-process gloo job on one GPU: a `train_step` under `-l <loss>` on its shard of `_make`'s batch (shared with
+    tests/test_gpu_fape.py)."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0",
                       PTAMD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     import sys
@@ -508,13 +510,13 @@ def _dp_worker(rank, world, port, out_dir):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     dp.init_from_env()
-    model, opt, args, batch, lens = _make(dev, "slddt")
+    model, opt, args, batch, lens = _make(dev, loss)
     dp.attach(model)
     (seq, ang, crd), n_res = base._shard(batch, lens, world, rank)
     assert seq.shape[0] == (3 if rank == 0 else 2)
     losses = train_step(model, opt, args, seq.to(dev), ang.to(dev), crd.to(dev), n_res=n_res)
     np.save(os.path.join(out_dir, f"flat{rank}.npy"), model.flat_parameters()[0].cpu().numpy())
-    np.save(os.path.join(out_dir, f"loss{rank}.npy"), np.array([float(losses[k]) for k in KEYS]))
+    np.save(os.path.join(out_dir, f"loss{rank}.npy"), np.array([float(losses[k]) for k in keys]))
     np.save(os.path.join(out_dir, f"held{rank}.npy"), np.array([lens.index(2) in dp.shard_indices(lens, world, rank)]))
     dp.barrier()
     dp.shutdown()

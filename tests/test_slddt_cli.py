@@ -134,6 +134,9 @@ def test_host_mirror_signatures_and_no_cpu_path(built_lib):
     assert sig["cutoff"].default == 15.0 and sig["temperature"].default == 1.0
     assert inspect.signature(losses.batch_loss).parameters["slddt"].default is None       # today's calls are untouched
     assert inspect.signature(losses.LossReport.__init__).parameters["slddt"].default is None
-    assert losses.LossReport._NVEC == 25
+    assert losses.VECTOR_SIZE == 27 and losses.VECTOR_SLOTS == {        # the reduced vector: every slot where it has always been
+        "sums": slice(0, 4), "proteins": slice(4, 5), "rmsd_sum": slice(5, 6), "mse": slice(6, 12), "status_bits": slice(12, 16),
+        "residues": slice(16, 17), "rmsd_proteins": slice(17, 18), "ranks_counted": slice(18, 19), "lddt": slice(19, 23),
+        "slddt": slice(23, 25), "fape": slice(25, 27)}
     with pytest.raises(RuntimeError, match="device tensors only"):      # a missing GPU is an error, never a CPU fall-back
         losses.slddt_forward_backward(torch.zeros(1, 28, 3), torch.zeros(1, 28, 3), torch.zeros(1, 2, dtype=torch.int64))
