@@ -239,6 +239,54 @@ int ptamd_fape_fwd_bwd(const float *pred_crd, const float *true_crd, const int64
                        float *stats, int64_t *npairs, int64_t *nclamped, float *dcrd, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* Symmetric side-chain renaming of the ground truth, for a whole batch (csrc/rename.hip): `train.py --rename_symmetric`.  The
+ * reference has no counterpart.  ASP, GLU, PHE and TYR have side chains with a 180 degree symmetry: OD1/OD2, OE1/OE2, CD1/CD2 and
+ * CE1/CE2 are chemically the same atoms, which of them carries which name in a deposited structure is arbitrary, and chi and
+ * chi + pi build the same molecule with the names exchanged.  This is the renaming of Jumper et al., "Highly accurate protein
+ * structure prediction with AlphaFold", Nature 596:583-589 (2021), supplementary 1.8.5, algorithm 26: the truth is renamed,
+ * residue by residue, to the naming that agrees better with the prediction, and every loss and metric then runs against the
+ * renamed truth unchanged.
+ *   Swap pairs.  Slots are 0 N, 1 CA, 2 C, 3 O, 4 + k for side-chain atom k; residue ids follow ACDEFGHIKLMNPQRSTVWY.
+ *     ASP (2):  (6,7) OD1/OD2;                    chi column 8
+ *     GLU (3):  (7,8) OE1/OE2;                    chi column 9
+ *     PHE (4):  (6,10) CD1/CD2, (7,9) CE1/CE2;    chi column 8
+ *     TYR (19): (6,11) CD1/CD2, (7,10) CE1/CE2;   chi column 8
+ *   The chi column is the angle column (of 12) whose torsion places the first atom of the first pair - side-chain atom k is
+ *   placed with column 6 + k (csrc/geometry.hip; column 6 is CB's own torsion, so what the literature calls chi2 of ASP is
+ *   column 8): turning it by pi builds the residue with the names exchanged.  An AMBIGUOUS atom is a member of a swap pair, in a
+ *   candidate residue or not.  No other residue type is touched (ARG, LEU and VAL are not symmetric in this sense).
+ *   Present atoms.  Exactly the atoms of ptamd_lddt, ptamd_slddt_fwd_bwd and ptamd_fape_fwd_bwd: slots of non-pad residues
+ *   whose true coordinate has no NaN (csrc/atom_tiles.h decides).
+ *   Candidate residue.  A non-pad ASP, GLU, PHE or TYR ALL of whose ambiguous atoms are present.  Every other residue is left as
+ *   it is, with flag 0 and cost 0.  (Simpler than AlphaFold's partial-presence handling through alt_gt_exists: a residue with a
+ *   missing swap partner keeps its names.)
+ *   Cost.  Over the ambiguous atoms a of a candidate residue, a' the partner of a:
+ *     cost_orig = sum_a sum_q |d_pred(a,q) - d_true(a,q)|,   cost_alt = sum_a sum_q |d_pred(a,q) - d_true(a',q)|,
+ *   q over every present, non-ambiguous atom of the protein, those of the residue itself included; d = sqrt(dx^2 + dy^2 + dz^2)
+ *   of fp32 coordinate differences, prediction and truth through the same expression (algorithm 26 without the 1e-10 that the
+ *   published code adds under the root).  Sums: fp32 within a tile of 64 partners, fp64 beyond, rounded once.
+ *   Decision.  swapped = cost_alt < cost_orig on the reported fp32 values; strict, so a tie keeps the names.  A present atom
+ *   whose predicted coordinate is not finite or beyond 1e18 in magnitude (the test of the two training losses) leaves the WHOLE
+ *   protein unswapped: flags 0, and cost = NaN for its candidates.  Nothing traps, other proteins are untouched.
+ *   Application.  true_crd_out [B,L*14,3]: a copy of true_crd with the slot pairs of swapped residues exchanged; NaNs, padding
+ *   and every other value are copied bit for bit.  true_ang_out [B,L,24] (cos and sin interleaved): a copy of true_ang with
+ *   both entries of the chi column of swapped residues negated (the sign bit flipped: NaN stays NaN); true_ang and true_ang_out
+ *   are optional, both NULL or neither.
+ *   Gradient.  The renaming is a constant for the gradient (a stop-gradient, as in AlphaFold): there is no adjoint.
+ *   swapped [B,L] out (int32: 0 or 1), cost [B,L,2] out = {cost_orig, cost_alt}; both written for every residue.
+ * No atomics and fixed-order sums: two runs give the same bits, and a protein's result depends neither on the batch around it
+ * nor on how far its row is padded.  Workspace: a function of (B, L) only - 32 B per atom slot, 40 B per residue and 1 KB per
+ * (tile of 64 swap pairs, chunk of 4 tiles of 64 atoms); B = 32, L = 512: 23e6 bytes.  No getenv, no state between calls.
+ * B or L <= 0, L beyond INT_MAX / 28 (the bound of ptamd_lddt), a NULL array other than the angle pair, only one of true_ang and
+ * true_ang_out NULL, an output that overlaps its input, or true_crd_out overlapping pred_crd: PTAMD_ERR_BAD_SHAPE; workspace NULL
+ * or too small: PTAMD_ERR_WORKSPACE; a workspace that is not 16-byte aligned: PTAMD_ERR_ALIGN; nothing is launched or written in
+ * any of these cases.  The partial sums grow with L^2 (pair tiles x atom chunks: 175 MB per protein at L = 10000), and the sweep's
+ * grid covers the largest protein the shape allows - workgroups beyond a protein's own pairs and atoms return at once. */
+size_t ptamd_rename_symmetric_workspace_bytes(int B, int L);
+int ptamd_rename_symmetric(const float *pred_crd, const float *true_crd, const float *true_ang, const int64_t *seq, int B, int L,
+                           float *true_crd_out, float *true_ang_out, int32_t *swapped, float *cost, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* mse_over_angles x3 (losses.py:175-214; train.py:64-66) in one pass.
  *   pred, truth [T,24]; out[6] = {sum_full, cnt_full, sum_bb, cnt_bb, sum_sc, cnt_sc} (fp32); the workspace holds
  *   the fp64 partial sums of the first pass */

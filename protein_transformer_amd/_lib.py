@@ -132,6 +132,8 @@ SIGNATURES = {
     "ptamd_slddt_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "ptamd_fape_workspace_bytes": (_sz, [_i, _i]),
     "ptamd_fape_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "ptamd_rename_symmetric_workspace_bytes": (_sz, [_i, _i]),
+    "ptamd_rename_symmetric": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "ptamd_mse_angles_workspace_bytes": (_sz, []),
     "ptamd_mse_angles_fwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),
     "ptamd_mse_angles_bwd": (_i, [_p, _p, _i64, _p, _f, _i, _p, _p]),

@@ -131,6 +131,43 @@ def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
     return stats, npairs, nclamped, dcrd
 
 
+# ----------------------------------------------------------------------------- symmetric side chains
+# residue id -> (swap pairs as atom slots, the angle column whose torsion turns by pi when the names are exchanged); the table of
+# include/ptamd.h.  The names behind the slots are protein/PDB_Creator.py's (tests/test_rename_cli.py derives the table from them).
+SYMMETRIC_SWAPS = {2: (((6, 7),), 8), 3: (((7, 8),), 9), 4: (((6, 10), (7, 9)), 8), 19: (((6, 11), (7, 10)), 8)}
+
+
+def rename_symmetric(crd, true_crds, seq, true_ang=None):
+    """The truth of a batch under the naming of its symmetric side chains (ASP, GLU, PHE, TYR) that agrees better with the
+    prediction `crd` (csrc/rename.hip; definition in include/ptamd.h; AlphaFold 2's algorithm 26; no counterpart in the reference).
+    crd, true_crds [B,L*14,3], seq [B,L], true_ang [B,L,24] (cos, sin interleaved) or None.  Returns (true_crds', true_ang' or
+    None, swapped [B,L] int32, cost [B,L,2] = {orig, alt}): new tensors, the inputs are untouched.  A constant for the gradient.
+    No host synchronisation."""
+    _lib.require_gpu(crd, true_crds, seq, true_ang)
+    B, L = seq.shape
+    crd, true_crds, seq = crd.detach().float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    crd_out = torch.empty_like(true_crds)
+    ang_out = None
+    if true_ang is not None:
+        true_ang = true_ang.float().contiguous()
+        assert true_ang.shape == (B, L, NUM_PREDICTED_ANGLES * 2)
+        ang_out = torch.empty_like(true_ang)
+    swapped = torch.empty(B, L, dtype=torch.int32, device=seq.device)
+    cost = torch.empty(B, L, 2, dtype=torch.float32, device=seq.device)
+    ws = _lib.workspace("rename_symmetric", _lib.lib().ptamd_rename_symmetric_workspace_bytes(B, L), seq.device)
+    rc = _lib.lib().ptamd_rename_symmetric(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(true_ang), _lib.ptr(seq), B, L,
+                                           _lib.ptr(crd_out), _lib.ptr(ang_out), _lib.ptr(swapped), _lib.ptr(cost), _lib.ptr(ws),
+                                           ws.numel(), _lib.stream())
+    _lib.check(rc, "rename_symmetric")
+    return crd_out, ang_out, swapped, cost
+
+
+# batch_loss's keyword `rename_symmetric` (the name the command line and the callers use) hides the function inside batch_loss:
+# this alias is how batch_loss, and nobody else, reaches it
+_rename_truth = rename_symmetric
+
+
 # ----------------------------------------------------------------------------- the extra structural losses
 # All the host code knows about a structural loss beside the dRMSD family (`train.py -l <name>`; the name is also its keyword in
 # `batch_loss` and `LossReport` and its key in `LossReport.wait()`).  run(crd, true_crds, seq, need_grad, params) -> (per-protein
@@ -158,6 +195,12 @@ EXTRA_LOSSES = {e.name: e for e in (
               "-l fape needs every atom: it cannot be combined with --backbone_loss "
               "(a backbone FAPE needs the compact backbone layout and does not exist here)"),
 )}
+
+
+RENAME_BACKBONE_MESSAGE = ("--rename_symmetric renames side-chain atoms: it cannot be combined with --backbone_loss "
+                           "(no side chains are built there)")
+RENAME_NO_STRUCTURE_MESSAGE = ("--rename_symmetric compares the truth with the predicted structure: it cannot be combined with "
+                               "-l mse, whose training steps build no structure")
 
 
 class _DrmsdFn(torch.autograd.Function):
@@ -218,7 +261,8 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
     return generate_coords(angles, seq)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None, fape=None):
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None, fape=None,
+               rename_symmetric=False, true_ang=None):
     """Device-resident core of compute_batch_drmsd: no host synchronisation.
 
     Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
@@ -235,16 +279,27 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     comparable between runs), and the per-protein losses [B] (NaN for a protein without one) are appended as the last value.
       `slddt` = (cutoff, temperature): the smooth lDDT loss of csrc/slddt.hip (`train.py -l slddt`).
       `fape` = clamp in Angstrom: the frame aligned point error of csrc/fape.hip (`train.py -l fape`).
+
+    `rename_symmetric` (`train.py --rename_symmetric`; off: nothing above changes and nothing more is launched): the truth is
+    renamed once, against the coordinates just built (`rename_symmetric` above) - the dRMSD statistics, the extra loss and all
+    gradients use the renamed truth, which is a constant for the gradient.  The renamed truth [B,L*14,3] and the renamed `true_ang`
+    ([B,L,24]; None when `true_ang` was not given) are appended behind everything else, for the caller's RMSD, lDDT and MSE.
+    Refused together with `backbone_only`: no side chains are built there.
     """
     given = [(EXTRA_LOSSES[name], params) for name, params in (("slddt", slddt), ("fape", fape)) if params is not None]
     assert len(given) <= 1, "one structural loss at a time"
     extra, params = given[0] if given else (None, None)
     assert extra is None or not backbone_only, extra.backbone_message
+    assert not (rename_symmetric and backbone_only), RENAME_BACKBONE_MESSAGE
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
     crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
+    renamed = ()
+    if rename_symmetric:
+        true_crds, true_ang = _rename_truth(crd, true_crds, input_seqs, true_ang)[:2]
+        renamed = (true_crds, true_ang)
     stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward and extra is None,
                                          backbone_only=backbone_only)
     if extra is not None:
@@ -254,7 +309,7 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
     out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
-    return out if extra is None else out + (per_protein,)
+    return (out if extra is None else out + (per_protein,)) + renamed
 
 
 # ----------------------------------------------------------------------------- statistics hand-over

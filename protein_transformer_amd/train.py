@@ -28,7 +28,8 @@ from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
 from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging,
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
-from .losses import EXTRA_LOSSES, LossReport, batch_loss, combine_drmsd_mse, mse_grad, mse_sums
+from .losses import (EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE, RENAME_NO_STRUCTURE_MESSAGE, LossReport, batch_loss, combine_drmsd_mse,
+                     mse_grad, mse_sums)
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
 from .optim import FusedAdam, FusedSGD, ScheduledOptim
@@ -124,6 +125,11 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     are taken forward-only on the coordinates already built, as is the loss itself in `eval_mode`.  Under any other `-l` no key.
       slddt: the smooth lDDT loss of csrc/slddt.hip (`--slddt_cutoff`, `--slddt_temperature`; definition in include/ptamd.h).
       fape: the frame aligned point error of csrc/fape.hip (`--fape_clamp`): it alone tells a structure from its mirror image.
+
+    `args.rename_symmetric` (losses.rename_symmetric; not in the reference): the structure is built first and the truth - coordinates
+    and angles - renamed against it at its symmetric side chains (ASP, GLU, PHE, TYR); every number above, every gradient, the MSE,
+    `rmsd-full` and the lDDT are then taken against the renamed truth.  No key is added.  Refused with `args.backbone_loss` and
+    wherever no structure is built (a training step of `-l mse`).  Without the flag, order and calls are what they were.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
@@ -133,8 +139,24 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     if extra is not None and backbone:
         raise ValueError(extra.backbone_message)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
+    rename = bool(getattr(args, "rename_symmetric", False))
+    if rename and (backbone or not need_drmsd):
+        raise ValueError(RENAME_BACKBONE_MESSAGE if backbone else RENAME_NO_STRUCTURE_MESSAGE)
     sums = stats = grad = status = rmsd = lddt = per_protein = None
-    if not empty:
+    if not empty and rename:
+        # the structure and the renaming come first: the MSE, the RMSD and the lDDT below see the renamed truth
+        *head, tgt_crds, tgt_ang = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True, rename_symmetric=True,
+                                              true_ang=tgt_ang, **({extra.name: extra.params(args)} if extra is not None else {}))
+        stats, grad, status, crd = head[:4]
+        per_protein = head[4] if extra is not None else None
+        sums = mse_sums(pred, tgt_ang)
+        if return_rmsd:
+            from .eval_metrics import kabsch_rmsd_batch
+            rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
+        if want_lddt:
+            from .eval_metrics import lddt_batch
+            lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
+    elif not empty:
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
             if extra is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the extra loss
@@ -492,6 +514,8 @@ class _Parser(argparse.ArgumentParser):
         a = super().parse_args(args, namespace)
         extra = EXTRA_LOSSES.get(a.loss)
         problem = extra and (extra.backbone_message if a.backbone_loss else extra.check(extra.params(a)))
+        if not problem and a.rename_symmetric:      # (a training step under -l mse builds no structure; evaluation always does)
+            problem = RENAME_BACKBONE_MESSAGE if a.backbone_loss else RENAME_NO_STRUCTURE_MESSAGE if a.loss == "mse" else None
         if problem:
             self.error(problem)
         return a
@@ -591,6 +615,9 @@ def create_parser():
                      help="-l slddt: temperature of the four sigmoids (1 = AlphaFold 3; smaller approaches the hard lDDT).")
     new.add_argument("--fape_clamp", type=float, default=10.0,
                      help="-l fape: the clamp of the frame aligned point error, in Angstrom (inf = unclamped).")
+    new.add_argument("--rename_symmetric", action="store_true",
+                     help="rename the truth at its symmetric side chains (ASP, GLU, PHE, TYR) to the naming that agrees better with "
+                          "the prediction, before every loss and metric (AlphaFold 2, algorithm 26); not with --backbone_loss or -l mse")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
