@@ -96,7 +96,9 @@ int ptamd_nerf_bb_bwd(const float *ang, const int64_t *seq, const float *crd_bb,
  *   pred_crd, true_crd [B,L*14,3]; NaN in true_crd = atom absent.
  *   stats [B,8] out: {drmsd, drmsd/n, bb_drmsd, bb_drmsd/n_bb, n, n_bb, 0, 0}
  *   dcrd [B,L*14,3] out or NULL: d(drmsd/n)/d(pred_crd)  (the reference always
- *   differentiates the length-normalised loss, losses.py:80,91-92).
+ *   differentiates the length-normalised loss, losses.py:80,91-92).  A protein with fewer than two present atoms has no pair:
+ *   its dcrd is all zeros and its drmsd, drmsd/n are NaN (the mean over an empty set, as in the reference); likewise the two
+ *   backbone statistics with fewer than two present backbone atoms.  The other proteins of the batch are not affected.
  * Workspace: 52 B per atom slot (compacted copies: predicted coordinates, (predicted, true) interleaved per axis, index) plus
  * the fixed-order partial sums of the upper-triangle sweep - one 1 KB column partial per (4-row-tile strip, 64-atom column
  * tile) and one 4 KB row partial per (strip, chunk of 8 column tiles): O(n^2 / 256) per protein (n = 14 L atom slots) -

@@ -528,9 +528,9 @@ __global__ __launch_bounds__(CB) void drmsd_finalize_kernel(const Counts *__rest
       st[6] = 0.f;
       st[7] = 0.f;
     }
-    // backbone-only loss: fewer than two present atoms = no pair - the protein contributes a zero gradient (its statistics are
-    // the NaN of a mean over an empty set, as in the reference)
-    s_scale = (SPR == BB_SLOTS && cn.n < 2) ? 0.f : (float)(1.0 / (n * P * (double)D));
+    // fewer than two present atoms = no pair - the protein contributes a zero gradient in both instantiations (its statistics
+    // are the NaN of a mean over an empty set, as in the reference; 1 / (n P D) would be NaN and reach the one present atom)
+    s_scale = cn.n < 2 ? 0.f : (float)(1.0 / (n * P * (double)D));
   }
   if (dcrd == nullptr) return;
   __syncthreads();
