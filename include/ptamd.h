@@ -136,7 +136,9 @@ int ptamd_drmsd_bb_fwd_bwd_budget(const float *pred_bb, const float *true_crd, c
 
 /* rmsd (losses.py:281-286, ProDy calcTransformation + calcRMSD) for a whole batch: RMSD of the predicted atoms after optimal
  * rigid superposition (Kabsch) onto the true ones, over the atoms whose truth is present (NaN = absent), residues with
- * PTAMD_PAD_ID skipped.  rmsd [B] out (NaN for a protein without atoms).  One workgroup per protein, fp64 moments. */
+ * PTAMD_PAD_ID skipped.  rmsd [B] out (NaN for a protein without atoms).  One workgroup per protein, fp64 moments.
+ * A NaN or infinite coordinate on a present atom gives that protein NaN (never 0); finite ones of any size (1e30) are used as
+ * they are; what absent slots and padded residues hold is never read into the result. */
 int ptamd_kabsch_rmsd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *rmsd,
                       void *stream);
 
@@ -291,11 +293,15 @@ int ptamd_rename_symmetric(const float *pred_crd, const float *true_crd, const f
 
 /* mse_over_angles x3 (losses.py:175-214; train.py:64-66) in one pass.
  *   pred, truth [T,24]; out[6] = {sum_full, cnt_full, sum_bb, cnt_bb, sum_sc, cnt_sc} (fp32); the workspace holds
- *   the fp64 partial sums of the first pass */
+ *   the fp64 partial sums of the first pass.  A row enters a slice when any truth element of the slice is != 0: NaN and a
+ *   denormal (1e-40: nothing flushes to zero) select it, -0.0 does not; its NaN truth elements are left out of sum and count.
+ *   T <= 0: PTAMD_ERR_BAD_SHAPE; pred or truth not 16-byte aligned: PTAMD_ERR_ALIGN; workspace NULL or short:
+ *   PTAMD_ERR_WORKSPACE; nothing is launched or written then. */
 size_t ptamd_mse_angles_workspace_bytes(void);
 int ptamd_mse_angles_fwd(const float *pred, const float *truth, int64_t T, float *out, void *workspace,
                          size_t workspace_bytes, void *stream);
-/* dpred[T,24] (+)= coef * 2*(pred-truth)/cnt_full on the selected elements; accumulate != 0 adds */
+/* dpred[T,24] (+)= coef * 2*(pred-truth)/cnt_full on the selected elements; accumulate != 0 adds.  Every other element is
+ * exactly 0 (accumulating: unchanged), also when cnt_full = sums[1] is 0.  No alignment requirement; T <= 0: PTAMD_ERR_BAD_SHAPE. */
 int ptamd_mse_angles_bwd(const float *pred, const float *truth, int64_t T, const float *sums, float coef,
                          int accumulate, float *dpred, void *stream);
 

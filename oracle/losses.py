@@ -59,6 +59,8 @@ def kabsch_rmsd(a, b):
     """
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return float("nan")                      # as the device kernel: a non-finite coordinate is no perfect score
     ac, bc = a - a.mean(0), b - b.mean(0)
     u, s, vt = np.linalg.svd(ac.T @ bc)
     d = np.sign(np.linalg.det(u @ vt))

@@ -89,7 +89,10 @@ __global__ __launch_bounds__(KB) void kabsch_rmsd_kernel(const float *__restrict
     m[k] = v;
   }
   const double n = m[0];
-  if (n < 1.0) {
+  // no atoms, or a NaN / infinite coordinate on a present atom (it reaches sum |a|^2 or sum |b|^2, both sums of squares, so
+  // nothing cancels): NaN.  Without this test the fmax(., 0) below turn NaN moments into an RMSD of 0.  Finite fp32
+  // coordinates of any size keep every moment finite in fp64.
+  if (n < 1.0 || !isfinite(m[16] + m[17])) {
     out[b] = __builtin_nanf("");
     return;
   }
