@@ -314,6 +314,9 @@ int ptamd_mse_angles_bwd(const float *pred, const float *truth, int64_t T, const
  * epilogue, in order: + bias[N] (may be NULL); ReLU if (flags & PTAMD_EPI_RELU);
  *   dropout(p, seed, stream_id) if p > 0;  + residual[M,N] (ldr; may be NULL), or the ReLU/dropout gate of
  *   PTAMD_EPI_GATE;  tanh if (flags & PTAMD_EPI_TANH).
+ * A leading dimension may exceed the extent of its rows (what lies between is neither read into the result nor written) but not
+ * fall short of it: lda, ldb, ldc or (with a residual) ldr - and `ld` of ptamd_hp_split / a split job - smaller than the row it
+ * strides is PTAMD_ERR_BAD_SHAPE in ptamd_gemm, ptamd_gemm_group, ptamd_gemm_hp and the hp split entry points; nothing is launched.
  * Replaces torch.nn.Linear (Attention.py:49,69; Sublayers.py:34; encoder_only.py:39)
  * and their autograd backward GEMMs. */
 #define PTAMD_EPI_RELU 1

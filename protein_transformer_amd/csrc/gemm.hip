@@ -425,6 +425,10 @@ int build_params(const ptamd_gemm_args *a, GemmParams &p, int &splits, int &mode
   if ((!a->a_kmajor || !a->b_kmajor) && (a->K & 3)) return PTAMD_ERR_BAD_SHAPE;  // K-contiguous rows are read 16 B at a time
   if (a->a_kmajor && (a->M & 3)) return PTAMD_ERR_BAD_SHAPE;
   if (a->b_kmajor && (a->N & 3)) return PTAMD_ERR_BAD_SHAPE;
+  // a row has to fit in its stride: a shorter one would alias the rows of an operand or let rows of C overwrite each other
+  if (a->lda < (a->a_kmajor ? a->M : a->K) || a->ldb < (a->b_kmajor ? a->N : a->K) || a->ldc < a->N ||
+      (a->residual && a->ldr < a->N))
+    return PTAMD_ERR_BAD_SHAPE;
   if (!pt_aligned16(a->A) || !pt_aligned16(a->B)) return PTAMD_ERR_ALIGN;
   if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return PTAMD_ERR_BAD_SHAPE;
   splits = a->split_k > 1 ? a->split_k : 1;

@@ -810,6 +810,7 @@ int ptamd_hp_padded_rows(int rows) { return rows <= 0 ? 0 : round_up(rows, 32); 
 
 int ptamd_hp_split(const float *x, int ld, int rows, int K, int transposed, void *planes, float *scale, void *stream) {
   if (rows <= 0 || K <= 0 || !x || !planes || !scale) return PTAMD_ERR_BAD_SHAPE;
+  if (ld < (transposed ? rows : K)) return PTAMD_ERR_BAD_SHAPE;  // a row of x has to fit in its stride
   if (!transposed && ((ld & 3) || (K & 3) || !pt_aligned16(x))) return PTAMD_ERR_ALIGN;
   if (!pt_aligned16(planes)) return PTAMD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
@@ -838,7 +839,8 @@ int ptamd_hp_split_rows(const ptamd_hp_split_job *jobs, int njobs, void *stream)
   int blocks = 0, kmax = 0;
   for (int i = 0; i < njobs; ++i) {
     const ptamd_hp_split_job &q = jobs[i];
-    if (!q.x || !q.planes || !q.scale || q.rows <= 0 || q.K <= 0 || (q.K & 3) || (q.ld & 3) || q.K > 2048) return PTAMD_ERR_BAD_SHAPE;
+    if (!q.x || !q.planes || !q.scale || q.rows <= 0 || q.K <= 0 || (q.K & 3) || (q.ld & 3) || q.K > 2048 || q.ld < q.K)
+      return PTAMD_ERR_BAD_SHAPE;
     if (!pt_aligned16(q.x) || !pt_aligned16(q.planes)) return PTAMD_ERR_ALIGN;
     j.x[i] = q.x; j.planes[i] = static_cast<char *>(q.planes); j.scale[i] = q.scale;
     j.ld[i] = q.ld; j.rows[i] = q.rows; j.K[i] = q.K;
@@ -881,6 +883,8 @@ size_t ptamd_gemm_hp_workspace_bytes(int M, int N, int split_k) { return (M <= 0
 int ptamd_gemm_hp(const ptamd_gemm_hp_args *a, void *stream) {
   if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0) return PTAMD_ERR_BAD_SHAPE;
   if (!a->A || !a->B || !a->A_scale || !a->B_scale || !a->C) return PTAMD_ERR_BAD_SHAPE;
+  // a row has to fit in its stride (with kv_planes only the columns in front of kv_col0 are stored in C)
+  if (a->ldc < (a->kv_planes ? a->kv_col0 : a->N) || (a->residual && a->ldr < a->N)) return PTAMD_ERR_BAD_SHAPE;
   if (!pt_aligned16(a->A) || !pt_aligned16(a->B)) return PTAMD_ERR_ALIGN;
   if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return PTAMD_ERR_BAD_SHAPE;
   if ((a->flags & PTAMD_EPI_GATE) && (a->residual == nullptr) == (a->gate_mask == nullptr)) return PTAMD_ERR_BAD_SHAPE;
