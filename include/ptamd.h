@@ -243,6 +243,49 @@ int ptamd_fape_fwd_bwd(const float *pred_crd, const float *true_crd, const int64
                        float *stats, int64_t *npairs, int64_t *nclamped, float *dcrd, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* Steric clash term, forward + analytic backward, for a whole batch (csrc/clash.hip): the auxiliary training term
+ * `--clash_weight` and the metric `--eval_clash`.  The reference has no counterpart, and every other loss and metric here
+ * compares the prediction with the truth; this one asks whether the predicted all-atom structure is physically possible.  It is
+ * the between-residue part of the structural violation loss of Jumper et al., "Highly accurate protein structure prediction
+ * with AlphaFold", Nature 596:583-589 (2021), supplementary 1.9.11 - the NeRF build fixes every bond length and bond angle, so a
+ * clash between residues is the only violation an angle model can commit.  The truth is not an argument.
+ *   Atoms.  Per protein, slot s of residue i is an atom when seq[i] is in 0..19 (neither PTAMD_PAD_ID nor an unknown id) and
+ *   s % 14 < 4 + ptamd_sidechain_atoms(seq[i]): the slot exists for that residue type.  This differs from ptamd_lddt and its
+ *   family, whose atoms are the truth's present atoms.  What any other slot holds (the NeRF build zero-fills them, so they all
+ *   coincide at the origin), NaN and 1e30 included, is never read and changes no output.
+ *   Radii.  The van der Waals radius by element, r = 1.7 A (C), 1.55 A (N), 1.52 A (O), 1.8 A (S); the element is the first
+ *   letter of the atom's name (ptamd_clash_radius below).
+ *   Pairs.  The unordered pairs {a, b} of atoms in DIFFERENT residues, except slot 2 (C) of residue i with slot 0 (N) of residue
+ *   i + 1 (the peptide bond) and slot 5 of a CYS (id 1) with slot 5 of any other CYS (a possible disulfide): AlphaFold's two
+ *   exclusions.  Pairs within a residue are never looked at.
+ *   Pair term.  v_ab = max(0, r_a + r_b - tau - d_ab) with the tolerance tau >= 0 (AlphaFold: 1.5 A) and d_ab = sqrt(|x_a -
+ *   x_b|^2 + 1e-30), the clamp under the root of the dRMSD and smooth-lDDT kernels.
+ *   Per-protein outputs.  loss_i = (1 / n_i) sum v_ab, n_i the protein's atom count: Angstrom per atom and, like lndrmsd,
+ *   independent of the length.  nclash_i is the number of pairs with v_ab > 0, an exact 64-bit integer.  A protein with atoms but
+ *   no violating pair has loss_i = 0; a protein without an atom has loss_i = NaN, nclash_i = 0 and a zero gradient.
+ *   Gradient.  g = d(loss_i)/d(pred_crd), analytic: atom a gets -(1 / n_i) sum_b [v_ab > 0] (x_a - x_b) / d_ab; atoms that
+ *   coincide exactly have a finite, zero share.  Exactly zero in every slot that is not an atom.
+ *   Unusable predictions.  An atom whose predicted coordinate is not finite or beyond 1e18 in magnitude makes the whole protein
+ *   unusable (the policy of ptamd_fape_fwd_bwd): loss_i = NaN, nclash_i = 0 and a zero gradient.  Nothing traps, other proteins
+ *   are untouched.
+ *   Batch.  The reported batch value is the mean over the proteins with a finite loss; the back-propagated quantity is the SUM
+ *   over proteins of loss_i, as for every structural loss here: data parallelism stays a plain SUM all-reduce.
+ *   stats [B,2] out = {loss_i, n_i}; nclash [B] out (int64).  dcrd [B,L*14,3], or NULL for the forward-only form (no gradient
+ *   work; the same bits in stats and nclash): with accumulate == 0 the call writes dcrd = weight * g (zeros where there is no
+ *   atom); with accumulate != 0 it computes dcrd += weight * g in place and touches the slots of atoms only - how the term joins
+ *   another loss's gradient in front of the one NeRF adjoint.
+ * No atomics and fixed-order partial sums: two runs give the same bits, and a protein's result depends neither on the batch
+ * around it nor on how far its row is padded.  Tile pairs whose bounding boxes of PREDICTED coordinates are farther apart than
+ * 2 * 1.8 - tau are skipped.  Workspace: a function of (B, L) only - that of ptamd_slddt_fwd_bwd and one int per protein;
+ * B = 32, L = 512: 162e6 bytes.  No getenv, no state between calls.  tolerance not finite or negative, weight not finite, a NULL
+ * array other than dcrd, B or L <= 0, or L beyond INT_MAX / 28 (the bound of ptamd_lddt): PTAMD_ERR_BAD_SHAPE; workspace NULL or
+ * too small: PTAMD_ERR_WORKSPACE; nothing is launched or written in either case.
+ * ptamd_clash_radius (host only): the radius of slot `slot` of residue type `residue`, -1 where the type has no such slot. */
+float ptamd_clash_radius(int residue, int slot);
+size_t ptamd_clash_workspace_bytes(int B, int L);
+int ptamd_clash_fwd_bwd(const float *pred_crd, const int64_t *seq, int B, int L, float tolerance, float weight, int accumulate,
+                        float *stats, int64_t *nclash, float *dcrd, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Symmetric side-chain renaming of the ground truth, for a whole batch (csrc/rename.hip): `train.py --rename_symmetric`.  The
  * reference has no counterpart.  ASP, GLU, PHE and TYR have side chains with a 180 degree symmetry: OD1/OD2, OE1/OE2, CD1/CD2 and
  * CE1/CE2 are chemically the same atoms, which of them carries which name in a deposited structure is arbitrary, and chi and

@@ -132,6 +132,9 @@ SIGNATURES = {
     "ptamd_slddt_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "ptamd_fape_workspace_bytes": (_sz, [_i, _i]),
     "ptamd_fape_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "ptamd_clash_radius": (_f, [_i, _i]),
+    "ptamd_clash_workspace_bytes": (_sz, [_i, _i]),
+    "ptamd_clash_fwd_bwd": (_i, [_p, _p, _i, _i, _f, _f, _i, _p, _p, _p, _p, _sz, _p]),
     "ptamd_rename_symmetric_workspace_bytes": (_sz, [_i, _i]),
     "ptamd_rename_symmetric": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "ptamd_mse_angles_workspace_bytes": (_sz, []),

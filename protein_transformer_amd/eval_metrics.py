@@ -10,6 +10,9 @@ round trip, no torch.linalg.
 lDDT (`lddt_batch`, `batch_lddt`; `train.py --eval_lddt`) has no counterpart in the reference: Mariani et al., Bioinformatics
 29(21):2722-2728 (2013), all-atom and C-alpha, per residue and per protein, counted on the device (csrc/lddt.hip; definition in
 include/ptamd.h).
+
+The steric clash term (`clash_batch`; `train.py --eval_clash`) has none either: the between-residue violation term of AlphaFold 2
+(Jumper et al. 2021, supplementary 1.9.11) on the predicted structure alone (csrc/clash.hip).
 """
 import numpy as np
 import torch
@@ -47,6 +50,16 @@ def lddt_batch(pred_crd, true_crd, seq, cutoff=15.0):
                                _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "lddt")
     return score, per_res, counts
+
+
+def clash_batch(crd, seq, tolerance=1.5):
+    """crd [B, L*14, 3] predicted coordinates (device), seq [B, L] -> (loss [B], nclash [B] int64, n_atoms [B]), all on the
+    device, no sync: the steric clash term of csrc/clash.hip (include/ptamd.h), forward only - Angstrom of overlap per atom
+    between atoms of different residues, the number of clashing pairs, and the atom count; NaN loss = no atom or an unusable
+    prediction.  The truth is not an argument (`train.py --eval_clash`)."""
+    from .losses import clash_forward_backward
+    stats, nclash, _ = clash_forward_backward(crd, seq, need_grad=False, tolerance=tolerance)
+    return stats[:, 0], nclash, stats[:, 1]
 
 
 def rmsd(a, b):

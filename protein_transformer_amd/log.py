@@ -23,6 +23,9 @@ _HISTORY = ("drmsd", "combined", "lndrmsd", "mse")
 # evaluation under `train.py --eval_lddt` only (no counterpart in the reference): present in a split's metrics once a batch has
 # reported them, as sum-<k> / n-<k> over the batches with a finite value and epoch-<k> = their mean
 _LDDT = ("lddt-full", "lddt-ca")
+# `train.py --eval_clash` (evaluation) and `--clash_weight` (every step): the steric clash term, kept exactly like the lDDT pair
+_CLASH = ("clash-full",)
+_OPTIONAL = _LDDT + _CLASH
 # `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
 # above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
 # exactly their keys
@@ -63,8 +66,8 @@ def reset_metrics_for_epoch(metrics, mode):
     m = metrics.setdefault(mode, _split_metrics(_extra(metrics.get("train", {}))))
     for k in _TRACKED + tuple(f"{x}-full" for x in _extra(m)):
         m[f"epoch-{k}"] = m[f"batch-{k}"] = 0
-    for k in _LDDT:
-        for prefix in ("epoch", "sum", "n"):
+    for k in _OPTIONAL:
+        for prefix in ("epoch", "batch", "sum", "n"):
             m.pop(f"{prefix}-{k}", None)
     m["batch-history"], m["speed-history"] = [], []
     m["batch-time"] = time.time()
@@ -89,9 +92,11 @@ def update_metrics(metrics, losses, mode, src_seq, tracking_loss=None, batch_lev
         if batch_level:
             m[f"batch-{x}-full"] = v
         m[f"epoch-{x}-full"] += v
-    for k in _LDDT:
+    for k in _OPTIONAL:
         if k in losses:                               # a batch without any scored protein reports NaN and is left out
             v = _num(losses[k])
+            if batch_level:                           # (training steps under --clash_weight: their rows carry the step's value)
+                m[f"batch-{k}"] = v
             m[f"sum-{k}"] = m.get(f"sum-{k}", 0.0) + (v if np.isfinite(v) else 0.0)
             m[f"n-{k}"] = m.get(f"n-{k}", 0) + int(np.isfinite(v))
     # residues of the GLOBAL batch: counted on the host before the upload and reduced with the loss statistics
@@ -115,7 +120,7 @@ def update_metrics_end_of_epoch(metrics, mode):
     for k in ("drmsd-full", "lndrmsd-full", "mse-full", "drmsd-bb", "lndrmsd-bb", "mse-bb", "mse-sc", "rmsd-full"):
         m[f"epoch-{k}"] /= n
     m["epoch-combined-full"] = 0 if m["epoch-drmsd-full"] == 0 else m["epoch-combined-full"] / n
-    for k in _LDDT:
+    for k in _OPTIONAL:
         if f"n-{k}" in m:
             m[f"epoch-{k}"] = m[f"sum-{k}"] / m[f"n-{k}"] if m[f"n-{k}"] else float("nan")
     for h in _HISTORY:
@@ -145,18 +150,20 @@ REFERENCE_CSV = False     # True: the granularity column carries upstream's lite
 
 def prepare_log_header(args):
     tail = ',lddt,lddt_ca' if getattr(args, "eval_lddt", False) else ''      # two trailing columns under --eval_lddt only
+    tail += ',clash' if getattr(args, "eval_clash", False) else ''            # one more, behind them, under --eval_clash only
     if args.loss == "combined":
         return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed' + tail
     return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed' + tail
 
 
-def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False):
+def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False):
     """One CSV row (log.py:115-130): ten values - drmsd, ln_drmsd, rmse, rmsd, combined, lr, mode, granularity, time,
     speed; like upstream the `combined` value is written whatever the header of `prepare_log_header` lists.  One
     deliberate difference: the granularity column says "batch" for per-batch rows (upstream writes the literal "epoch"
     in both cases, log.py:130) - unless `REFERENCE_CSV` is set (`train.py --reference-csv`), which reproduces the
     upstream column byte for byte for consumers of the reference's `.train` files.  `lddt` (`train.py --eval_lddt`): two
-    trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it)."""
+    trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it).  `clash`
+    (`train.py --eval_clash`): one more trailing value, the epoch's clash-full, nan on rows that have none."""
     t = t or time.time()
     m = metrics[mode]
     be = "epoch" if end_of_epoch else "batch"
@@ -167,6 +174,8 @@ def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False,
            m.get("speed", 0)]
     if lddt:
         row += [m.get(f"{be}-{k}", float("nan")) for k in _LDDT]
+    if clash:
+        row += [m.get(f"{be}-{k}", float("nan")) for k in _CLASH]
     log_writer.writerow(row)
 
 
@@ -178,7 +187,8 @@ def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer
     lr = optimizer.param_groups[0]["lr"]
     metrics["history-lr"].append(lr)
     if dp.is_main():
-        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)))
+        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)),
+                  clash=bool(getattr(args, "eval_clash", False)))
         if step % max(1, getattr(args, "log_wandb_step", 1) * 10) == 0:
             m = metrics["train"]
             print(f"  step {step:5d}  drmsd {m['batch-drmsd-full']:.4f}  ln {m['batch-lndrmsd-full']:.6f}  "
@@ -222,6 +232,6 @@ def do_eval_epoch_logging(metrics, mode):
     update_metrics_end_of_epoch(metrics, mode)
     if dp.is_main():
         m = metrics[mode]
-        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _LDDT if f"epoch-{k}" in m)      # --eval_lddt only
+        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _OPTIONAL if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash only
         print(f"  [{mode}] drmsd {m['epoch-drmsd-full']:.4f}  ln {m['epoch-lndrmsd-full']:.6f}  "
               f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}{tail}", flush=True)

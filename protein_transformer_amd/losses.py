@@ -131,6 +131,53 @@ def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
     return stats, npairs, nclamped, dcrd
 
 
+# ----------------------------------------------------------------------------- steric clashes
+CLASH_RADII = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}       # van der Waals radius by element, in Angstrom (include/ptamd.h)
+CLASH_TOLERANCE = 1.5                                           # AlphaFold 2's overlap tolerance, in Angstrom
+
+
+def clash_forward_backward(crd, seq, need_grad=True, tolerance=CLASH_TOLERANCE, weight=1.0, accumulate_into=None):
+    """Steric clash term of a batch of predicted structures (csrc/clash.hip; definition in include/ptamd.h; AlphaFold 2's
+    between-residue violation term; no counterpart in the reference).  crd [B,L*14,3], seq [B,L]; the truth is not an argument.
+    Returns (stats [B,2] = {loss_i, n_i}, nclash [B] int64, gradient or None).  The gradient is `weight` * d(loss_i)/d(crd) in a
+    new tensor, or - `accumulate_into`: a contiguous fp32 [B,L*14,3] tensor - added to that tensor in place, which is returned.
+    A protein without an atom or with an unusable prediction has a NaN loss and a zero gradient.  No host synchronisation."""
+    _lib.require_gpu(crd, seq, accumulate_into)
+    B, L = seq.shape
+    crd, seq = crd.float().contiguous(), seq.contiguous()
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3)
+    stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
+    nclash = torch.empty(B, dtype=torch.int64, device=seq.device)
+    dcrd = None
+    if accumulate_into is not None:
+        assert need_grad and accumulate_into.shape == crd.shape and accumulate_into.dtype == torch.float32 \
+            and accumulate_into.is_contiguous()
+        dcrd = accumulate_into
+    elif need_grad:
+        dcrd = torch.empty_like(crd)
+    ws = _lib.workspace("clash", _lib.lib().ptamd_clash_workspace_bytes(B, L), seq.device)
+    rc = _lib.lib().ptamd_clash_fwd_bwd(_lib.ptr(crd), _lib.ptr(seq), B, L, float(tolerance), float(weight),
+                                        int(accumulate_into is not None), _lib.ptr(stats), _lib.ptr(nclash), _lib.ptr(dcrd),
+                                        _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "clash_fwd_bwd")
+    return stats, nclash, dcrd
+
+
+CLASH_BACKBONE_MESSAGE = ("--clash_weight penalises clashes between side-chain and backbone atoms: it cannot be combined with "
+                          "--backbone_loss (no side chains are built there)")
+CLASH_NO_STRUCTURE_MESSAGE = ("--clash_weight penalises the predicted structure: it cannot be combined with -l mse, whose "
+                              "training steps build no structure")
+
+
+def clash_check(weight, tolerance):
+    """The parser's complaint about --clash_weight / --clash_tolerance, or None."""
+    if not (0 <= weight < np.inf):                                                  # (NaN fails)
+        return "--clash_weight must be finite and not negative"
+    if not (0 <= tolerance < np.inf):
+        return "--clash_tolerance must be finite and not negative"
+    return None
+
+
 # ----------------------------------------------------------------------------- symmetric side chains
 # residue id -> (swap pairs as atom slots, the angle column whose torsion turns by pi when the names are exchanged); the table of
 # include/ptamd.h.  The names behind the slots are protein/PDB_Creator.py's (tests/test_rename_cli.py derives the table from them).
@@ -262,7 +309,7 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
 
 
 def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None, fape=None,
-               rename_symmetric=False, true_ang=None):
+               clash=None, rename_symmetric=False, true_ang=None):
     """Device-resident core of compute_batch_drmsd: no host synchronisation.
 
     Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
@@ -285,12 +332,19 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     gradients use the renamed truth, which is a constant for the gradient.  The renamed truth [B,L*14,3] and the renamed `true_ang`
     ([B,L,24]; None when `true_ang` was not given) are appended behind everything else, for the caller's RMSD, lDDT and MSE.
     Refused together with `backbone_only`: no side chains are built there.
+
+    `clash` = (weight, tolerance) (`train.py --clash_weight`, `--clash_tolerance`; None: nothing above changes and nothing more is
+    launched): the steric clash term of csrc/clash.hip joins whichever loss trains the structure.  Its kernel runs after that loss
+    has produced the coordinate gradient and adds weight * d(sum_i clash_i) to it in place, so the one NeRF adjoint carries both
+    terms: the gradient is d(sum_i loss_i + weight * sum_i clash_i)/d(pred_sincos).  The per-protein clash losses [B] (unweighted;
+    NaN for a protein without one) are appended as the very last value.  Refused together with `backbone_only`.
     """
     given = [(EXTRA_LOSSES[name], params) for name, params in (("slddt", slddt), ("fape", fape)) if params is not None]
     assert len(given) <= 1, "one structural loss at a time"
     extra, params = given[0] if given else (None, None)
     assert extra is None or not backbone_only, extra.backbone_message
     assert not (rename_symmetric and backbone_only), RENAME_BACKBONE_MESSAGE
+    assert clash is None or not backbone_only, CLASH_BACKBONE_MESSAGE
     pred_sincos = pred_sincos.detach().float().contiguous()
     B, L = input_seqs.shape
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
@@ -304,12 +358,16 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
                                          backbone_only=backbone_only)
     if extra is not None:
         per_protein, dcrd = extra.run(crd, true_crds, input_seqs, do_backward, params)
+    clashes = ()
+    if clash is not None:
+        clashes = (clash_forward_backward(crd, input_seqs, need_grad=do_backward, tolerance=clash[1], weight=clash[0],
+                                          accumulate_into=dcrd if do_backward else None)[0][:, 0],)
     grad = None
     if do_backward:
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
     out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
-    return (out if extra is None else out + (per_protein,)) + renamed
+    return (out if extra is None else out + (per_protein,)) + renamed + clashes
 
 
 # ----------------------------------------------------------------------------- statistics hand-over
@@ -364,13 +422,32 @@ def _local_layout(B, present):
     return {name: at[name] for name in present}, size
 
 
-def pack_local(stats=None, mse=None, status=None, rmsd=None, channels=None, alloc=torch.empty):
+# The TAIL of a report: channel fields that lie behind everything above - behind the channel fields of a single process, behind
+# VECTOR_SLOTS under data parallelism - and only in the reports of callers that ASK for them (`tail`: {field: [B] or [B,k], or
+# None for a rank that has no value}; every rank of a job asks for the same fields, a rank with an empty shard included, so their
+# vectors have one length).  A report nobody asked a tail of has exactly the layout, the keys and the size it had before there
+# was one.  field -> the `wait()` keys of its columns:
+_TAIL_FIELDS = {"clash": ("clash",)}
+
+
+def _tail_layout(tail, start, width):
+    """{field asked for: its slice behind `start`}, end; width(field, tensor or None) -> words."""
+    at, size = _take([(field, width(field, t)) for field, t in (tail or {}).items()])
+    return {field: slice(start + s.start, start + s.stop) for field, s in at.items()}, start + size
+
+
+def pack_local(stats=None, mse=None, status=None, rmsd=None, channels=None, alloc=torch.empty, tail=None):
     """What a single process reports, in one fp32 buffer: stats [B,8], the six MSE sums, the status word (int32[1], as raw bits),
-    rmsd [B] and the `channels` ({field of _CHANNEL_FIELDS: [B] or [B,k]}), each of them or None.  One (asynchronous) copy per
-    field into `alloc(size)` (default: a host tensor); returns the buffer and its layout (B, {field that was passed: slice})."""
+    rmsd [B] and the `channels` ({field of _CHANNEL_FIELDS: [B] or [B,k]}), each of them or None; behind them the `tail` (above).
+    One (asynchronous) copy per field into `alloc(size)` (default: a host tensor); returns the buffer and its layout (B, {field
+    that was passed: slice}) - a tail field that was asked for without a value has an empty slice."""
     given = {k: t for k, t in dict(stats=stats, mse=mse, status=status, rmsd=rmsd, **(channels or {})).items() if t is not None}
-    B = next((t.shape[0] for name, t in given.items() if name not in ("mse", "status")), 0)
+    tailed = {field: t for field, t in (tail or {}).items() if t is not None}
+    B = next((t.shape[0] for name, t in {**given, **tailed}.items() if name not in ("mse", "status")), 0)
     at, size = _local_layout(B, tuple(given))
+    if tail:
+        tail_at, size = _tail_layout(tail, size, lambda field, t: 0 if t is None else len(_TAIL_FIELDS[field]) * B)
+        at, given = {**at, **tail_at}, {**given, **tailed}
     buf = alloc(size)
     for name, t in given.items():
         dst = buf.view(torch.int32) if name == "status" else buf
@@ -396,6 +473,10 @@ def unpack_local(host, layout, n_res=None):
         if field in at:
             values = host[at[field]].reshape(B, len(keys))
             out.update({key: finite_mean(values[:, k]) for k, key in enumerate(keys)})
+    for field, keys in _TAIL_FIELDS.items():
+        if field in at:                               # asked for: the keys exist, None when no value was passed
+            values = host[at[field]].reshape(-1, len(keys))
+            out.update({key: finite_mean(values[:, k]) if len(values) else None for k, key in enumerate(keys)})
     return out
 
 
@@ -406,10 +487,21 @@ VECTOR_SLOTS, VECTOR_SIZE = _take([("sums", 4), ("proteins", 1), ("rmsd_sum", 1)
                                   + [(field, 2 * len(keys)) for field, keys in _CHANNEL_FIELDS.items()])
 
 
-def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, channels=None, device=None):
-    """This rank's vector of VECTOR_SLOTS (arguments as `pack_local`; an empty shard passes None for everything).  No host sync."""
+def _vector_tail(tail):
+    """({field asked for: its slice behind VECTOR_SLOTS}, the vector's size): a field's `finite_sums`, whether or not the rank has a
+    value - the length depends on what was ASKED alone, so an empty shard adds a vector as long as the others'."""
+    return _tail_layout(tail, VECTOR_SIZE, lambda field, t: 2 * len(_TAIL_FIELDS[field]))
+
+
+def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, channels=None, device=None, tail=None):
+    """This rank's vector of VECTOR_SLOTS (arguments as `pack_local`; an empty shard passes None for everything - and, in `tail`,
+    None for every field the job asks for), with the tail's slots behind them.  No host sync."""
     S = VECTOR_SLOTS
-    v = torch.zeros(VECTOR_SIZE, dtype=torch.float64, device=device)
+    tail_at, size = _vector_tail(tail)
+    v = torch.zeros(size, dtype=torch.float64, device=device)
+    for field, at in tail_at.items():
+        if tail[field] is not None:
+            v[at] = finite_sums(tail[field])
     if stats is not None:
         v[S["sums"]], v[S["proteins"]] = stats[:, :4].double().sum(0), stats.shape[0]
     if rmsd is not None:
@@ -425,9 +517,10 @@ def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, chan
     return v
 
 
-def unpack_global(v, passed=()):
+def unpack_global(v, passed=(), tail=()):
     """The `LossReport.wait()` dictionary from the REDUCED vector (numpy fp64), the same on every rank.  A channel stays None unless
-    a protein of the global batch has a value (a rank with an empty shard reads it too) or this rank `passed` its field (then NaN)."""
+    a protein of the global batch has a value (a rank with an empty shard reads it too) or this rank `passed` its field (then NaN).
+    `tail`: the tail fields the job asked for, in the order of `reduce_vector` - their keys exist then, under the same rule."""
     one = {name: v[at][0] for name, at in VECTOR_SLOTS.items()}          # (the first entry of every slot: for the one-entry slots)
     out = dict(_NO_REPORT, n_proteins=int(one["proteins"]), mse=v[VECTOR_SLOTS["mse"]],
                status=sum(1 << k for k, n in enumerate(v[VECTOR_SLOTS["status_bits"]]) if n > 0),
@@ -439,6 +532,10 @@ def unpack_global(v, passed=()):
         total, count = v[VECTOR_SLOTS[field]].reshape(2, -1)
         out.update({key: total[k] / count[k] if count[k] > 0 else float("nan")
                     for k, key in enumerate(keys) if count[k] > 0 or field in passed})
+    for field, at in _vector_tail(dict.fromkeys(tail))[0].items():
+        total, count = v[at].reshape(2, -1)
+        out.update({key: total[k] / count[k] if count[k] > 0 else float("nan") if field in passed else None
+                    for k, key in enumerate(_TAIL_FIELDS[field])})
     return out
 
 
@@ -457,22 +554,28 @@ class LossReport:
     A rank whose shard is empty passes None for everything and still takes part in the reduction.
     """
 
-    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, lddt=None, slddt=None, fape=None):
+    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, clash=None, with_clash=False,
+                 lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
-        `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None."""
+        `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None.
+        `clash`: the per-protein clash losses [B] (`--clash_weight`, `--eval_clash`) or None; `with_clash`: the job reports them -
+        true on EVERY rank then, also on one whose shard is empty and has none: the report carries the tail for them, and `wait()`
+        the key `clash`."""
         self.world, self.n_res = dp.world_size(), n_res
         channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
+        tail = {"clash": clash} if with_clash or clash is not None else None
         if self.world == 1:
             buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
-                                     alloc=lambda n: _pinned("report32", n, torch.float32, device))
+                                     alloc=lambda n: _pinned("report32", n, torch.float32, device), tail=tail)
             self.global_mse_sums = mse_sums_local
             self._unpack = lambda: unpack_local(buf.numpy(), layout, n_res)
         else:
-            v = dp.all_reduce_sum_(reduce_vector(stats, mse_sums_local, status, rmsd, n_res, channels, device))
+            v = dp.all_reduce_sum_(reduce_vector(stats, mse_sums_local, status, rmsd, n_res, channels, device, tail=tail))
             self.global_mse_sums = v[VECTOR_SLOTS["mse"]].float()
-            buf = _pinned("report64", VECTOR_SIZE, torch.float64, device)
+            buf = _pinned("report64", v.numel(), torch.float64, device)
             buf.copy_(v, non_blocking=True)
-            self._unpack = lambda: unpack_global(buf.numpy().copy(), {field for field, t in channels.items() if t is not None})
+            passed = {field for field, t in {**channels, **(tail or {})}.items() if t is not None}
+            self._unpack = lambda: unpack_global(buf.numpy().copy(), passed, tuple(tail or ()))
         self._event = torch.cuda.Event()
         self._event.record()
 

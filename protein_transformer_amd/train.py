@@ -28,8 +28,8 @@ from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
 from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging,
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
-from .losses import (EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE, RENAME_NO_STRUCTURE_MESSAGE, LossReport, batch_loss, combine_drmsd_mse,
-                     mse_grad, mse_sums)
+from .losses import (CLASH_BACKBONE_MESSAGE, CLASH_NO_STRUCTURE_MESSAGE, CLASH_TOLERANCE, EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE,
+                     RENAME_NO_STRUCTURE_MESSAGE, LossReport, batch_loss, clash_check, combine_drmsd_mse, mse_grad, mse_sums)
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
 from .optim import FusedAdam, FusedSGD, ScheduledOptim
@@ -130,6 +130,14 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     and angles - renamed against it at its symmetric side chains (ASP, GLU, PHE, TYR); every number above, every gradient, the MSE,
     `rmsd-full` and the lDDT are then taken against the renamed truth.  No key is added.  Refused with `args.backbone_loss` and
     wherever no structure is built (a training step of `-l mse`).  Without the flag, order and calls are what they were.
+
+    `args.clash_weight` W > 0, `args.clash_tolerance` (losses.clash_forward_backward; AlphaFold 2's between-residue violation term;
+    not in the reference): the steric clash term joins whichever structural loss trains the structure.  The injected gradient gains
+    W * d(sum_i clash_i), the SUM over proteins like every other term, added to the coordinate gradient in front of the one NeRF
+    adjoint; `loss` gains W * clash-full, and the new key `clash-full` is the mean of the per-protein clash losses over the proteins
+    of the GLOBAL batch that have a finite one.  Refused with `args.backbone_loss` and with `-l mse`.  `args.eval_clash`: in
+    `eval_mode` the key `clash-full` is reported also when W = 0, from the coordinates already built.  With neither, nothing is
+    computed and the key is absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
@@ -142,11 +150,19 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     rename = bool(getattr(args, "rename_symmetric", False))
     if rename and (backbone or not need_drmsd):
         raise ValueError(RENAME_BACKBONE_MESSAGE if backbone else RENAME_NO_STRUCTURE_MESSAGE)
-    sums = stats = grad = status = rmsd = lddt = per_protein = None
+    clash_w, clash_tol = float(getattr(args, "clash_weight", 0.0)), float(getattr(args, "clash_tolerance", CLASH_TOLERANCE))
+    if clash_w > 0 and (backbone or not need_drmsd):
+        raise ValueError(CLASH_BACKBONE_MESSAGE if backbone else CLASH_NO_STRUCTURE_MESSAGE)
+    want_clash = clash_w > 0 or (eval_mode and bool(getattr(args, "eval_clash", False)))
+    ckw = {"clash": (clash_w, clash_tol)} if clash_w > 0 else {}      # (the term trains: batch_loss runs it on the gradient's way)
+    sums = stats = grad = status = rmsd = lddt = per_protein = clash = None
     if not empty and rename:
         # the structure and the renaming come first: the MSE, the RMSD and the lDDT below see the renamed truth
-        *head, tgt_crds, tgt_ang = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True, rename_symmetric=True,
-                                              true_ang=tgt_ang, **({extra.name: extra.params(args)} if extra is not None else {}))
+        res = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True, rename_symmetric=True,
+                         true_ang=tgt_ang, **({extra.name: extra.params(args)} if extra is not None else {}), **ckw)
+        if ckw:
+            *res, clash = res
+        *head, tgt_crds, tgt_ang = res
         stats, grad, status, crd = head[:4]
         per_protein = head[4] if extra is not None else None
         sums = mse_sums(pred, tgt_ang)
@@ -160,14 +176,16 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
         if need_drmsd:
             if extra is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the extra loss
-                stats, grad, status, crd, per_protein = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True,
-                                                                   **{extra.name: extra.params(args)})
+                stats, grad, status, crd, per_protein, *rest = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards,
+                                                                          return_crd=True, **{extra.name: extra.params(args)}, **ckw)
+                clash = rest[0] if ckw else None
             elif backbone and not eval_mode:
                 stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
                 crd = None
             else:
-                stats, grad, status, crd = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards and not backbone,
-                                                      return_crd=True)
+                stats, grad, status, crd, *rest = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards and not backbone,
+                                                             return_crd=True, **ckw)
+                clash = rest[0] if ckw else None
                 if backbone and do_backwards:              # evaluation that also back-propagates: the gradient is the backbone's
                     grad = batch_loss(pred, tgt_crds, src_seq, do_backward=True, backbone_only=True)[1]
             if return_rmsd:
@@ -181,8 +199,12 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
                 from .eval_metrics import lddt_batch
                 lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
+    if want_clash and not empty and clash is None:         # --eval_clash without the training term: on the coordinates already built
+        from .eval_metrics import clash_batch
+        clash = clash_batch(crd, src_seq, clash_tol)[0]
     report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
-                        **({extra.name: per_protein} if extra is not None else {}))
+                        **({extra.name: per_protein} if extra is not None else {}),
+                        **({"clash": clash, "with_clash": True} if want_clash else {}))
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -223,6 +245,10 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
     if extra is not None:
         out[f"{extra.name}-full"] = loss
+    if want_clash:      # --clash_weight, --eval_clash: one more key, the mean over the proteins of the GLOBAL batch that have a value
+        out["clash-full"] = channel("clash")
+        if clash_w > 0:
+            out["loss"] = loss + clash_w * out["clash-full"]
     if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
         out["lddt-full"], out["lddt-ca"] = channel("lddt"), channel("lddt-ca")
     if host["n_res"] is not None:
@@ -256,13 +282,15 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
         if args.eval_train:
             metrics = eval_epoch(model, train_eval_loader, device, args, metrics, mode="train", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
+            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
+                      clash=getattr(args, "eval_clash", False))
         if not args.train_only:
             for split, validation_data in validation_datasets.items():
                 metrics = eval_epoch(model, validation_data, device, args, metrics, mode=f"valid-{split}",
                                      pool=drmsd_worker_pool)
                 if dp.is_main():
-                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
+                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
+                      clash=getattr(args, "eval_clash", False))
         # every rank holds the same (globally reduced) metrics, so the scheduler, the early-stopping test and the
         # checkpoint policy below take the same branch on every rank
         if scheduler:
@@ -276,7 +304,8 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
     if not args.train_only and test_data is not None:
         metrics = eval_epoch(model, test_data, device, args, metrics, mode="test", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False))
+            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
+                      clash=getattr(args, "eval_clash", False))
     return metrics
 
 
@@ -516,6 +545,10 @@ class _Parser(argparse.ArgumentParser):
         problem = extra and (extra.backbone_message if a.backbone_loss else extra.check(extra.params(a)))
         if not problem and a.rename_symmetric:      # (a training step under -l mse builds no structure; evaluation always does)
             problem = RENAME_BACKBONE_MESSAGE if a.backbone_loss else RENAME_NO_STRUCTURE_MESSAGE if a.loss == "mse" else None
+        if not problem:
+            problem = clash_check(a.clash_weight, a.clash_tolerance)
+        if not problem and a.clash_weight > 0:
+            problem = CLASH_BACKBONE_MESSAGE if a.backbone_loss else CLASH_NO_STRUCTURE_MESSAGE if a.loss == "mse" else None
         if problem:
             self.error(problem)
         return a
@@ -618,6 +651,15 @@ def create_parser():
     new.add_argument("--rename_symmetric", action="store_true",
                      help="rename the truth at its symmetric side chains (ASP, GLU, PHE, TYR) to the naming that agrees better with "
                           "the prediction, before every loss and metric (AlphaFold 2, algorithm 26); not with --backbone_loss or -l mse")
+    new.add_argument("--clash_weight", type=float, default=0.0,
+                     help="W > 0: add W x the steric clash term (overlap of van der Waals spheres between residues, AlphaFold 2's "
+                          "between-residue violation term, in Angstrom per atom) to the structural loss; not with --backbone_loss or "
+                          "-l mse")
+    new.add_argument("--clash_tolerance", type=float, default=CLASH_TOLERANCE,
+                     help="--clash_weight, --eval_clash: the overlap that is tolerated, in Angstrom (1.5 = AlphaFold 2).")
+    new.add_argument("--eval_clash", action="store_true",
+                     help="evaluation also reports the steric clash term of the predicted structures: one more value on the "
+                          "per-epoch evaluation line, one trailing column in the .train log")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
