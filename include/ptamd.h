@@ -166,6 +166,40 @@ size_t ptamd_lddt_workspace_bytes(int B, int L);
 int ptamd_lddt(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float cutoff,
                int32_t *counts, float *per_res, float *score, void *workspace, size_t workspace_bytes, void *stream);
 
+/* TM-score and GDT_TS / GDT_HA over the C-alphas, for a whole batch (csrc/tmscore.hip): the metrics of `train.py --eval_tm`.
+ * The reference has no counterpart.  These are the scores CASP predictions are ranked by: Zhang & Skolnick, "Scoring function
+ * for automated assessment of protein structure template quality", Proteins 57:702-710 (2004), and the GDT counts of the same
+ * superposition search, as in the public TMscore program (zhanggroup.org/TM-score).  PARITY UNPINNED, like ptamd_kabsch_rmsd:
+ * no TM-score binary is at hand, so what is pinned is this definition, restated in numpy fp64 by tests/tm_ref.py.
+ *   Residues.  Per protein, the residues other than PTAMD_PAD_ID whose true C-alpha (slot 1 of the residue) has no NaN
+ *   coordinate - the presence rule of ptamd_kabsch_rmsd - taken in sequence order and compacted to indices 0..N-1; all fragment
+ *   arithmetic below is on compacted indices.  What the prediction holds never decides presence.  N < 3, or a non-finite
+ *   predicted coordinate on a present C-alpha: the three scores are NaN, counts = {N,0,0,0,0,0}, the transform is NaN.
+ *   Scales.  d0 = 1.24 (N - 15)^(1/3) - 1.8 for N > 21, floored at 0.5, and 0.5 for N <= 21; d_search = min(8, max(4.5, d0)).
+ *   Scoring a superposition (R, t).  d_i = |R p_i + t - q_i|, p the prediction, q the truth; TM(R,t) = (1/N) sum_i
+ *   1 / (1 + (d_i / d0)^2); c_k(R,t) = #{i : d_i <= k} for k in {0.5, 1, 2, 4, 8} A.
+ *   Seeds.  Fragment lengths l in {N, N>>1, N>>2, N>>3, N>>4, 4}, each raised to at least 4 (lowered to N when N = 3),
+ *   duplicates dropped; for each l every start s = 0..N-l is a seed; seeds are numbered in (l descending, s ascending) order.
+ *   Per seed.  (1) Superpose the fragment by least squares (proper rotation, det = +1) and score all N residues.  (2) Select
+ *   S = {i : d_i < d_search - 1}; while |S| < 3 raise that cutoff by 0.5 and reselect.  (3) Up to 20 times: superpose S and score
+ *   all N residues; reselect with cutoff d_search + 1 under the same widening rule; stop when S is unchanged.  Every (R,t) scored
+ *   in (1) and (3) is a VISITED superposition.
+ *   Results.  tm = max of TM over the visited superpositions; each count c_k is maximised separately over them, as the TMscore
+ *   program does; gdt_ts = (c1 + c2 + c4 + c8) / (4N), gdt_ha = (c0.5 + c1 + c2 + c4) / (4N); xform = the (R,t) of the
+ *   lowest-numbered seed, and within it the earliest iteration, that reaches tm.
+ *   score [B,3] out = {tm, gdt_ts, gdt_ha}; counts [B,6] out = {N, c0.5, c1, c2, c4, c8}; xform [B,12] out or NULL: R row-major,
+ *   then t, so that R p + t lies on q.
+ * Moments, rotations (Horn's quaternion matrix, cyclic Jacobi), distances and every threshold decision are fp64 on the fp32
+ * inputs, thresholds being tested on squared distances; scores are rounded to fp32 once.  No atomics, no order-dependent
+ * reduction: two runs give the same bits, and a protein's result does not depend on the batch around it.  A selection is kept as
+ * one bit per residue in the registers of a wavefront, which bounds L at 4096.  Workspace: 24 B per residue + 32 B per possible
+ * seed - a function of (B, L) only; B = 32, L = 512: 3.5e6 bytes.  A NULL array other than xform, B or L <= 0, or L > 4096:
+ * PTAMD_ERR_BAD_SHAPE; workspace NULL or too small: PTAMD_ERR_WORKSPACE; nothing is launched or written then.  No state
+ * between calls, nothing read from the environment. */
+size_t ptamd_tm_workspace_bytes(int B, int L);
+int ptamd_tm_score(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *score, int32_t *counts,
+                   float *xform, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
  * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
  * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the

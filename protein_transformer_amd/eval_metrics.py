@@ -13,6 +13,10 @@ include/ptamd.h).
 
 The steric clash term (`clash_batch`; `train.py --eval_clash`) has none either: the between-residue violation term of AlphaFold 2
 (Jumper et al. 2021, supplementary 1.9.11) on the predicted structure alone (csrc/clash.hip).
+
+TM-score and GDT_TS / GDT_HA (`tm_batch`, `batch_tm`; `train.py --eval_tm`) have none either: Zhang & Skolnick, Proteins
+57:702-710 (2004), over the C-alphas, maximised by the seed-and-refine superposition search of the TMscore program on the device
+(csrc/tmscore.hip; definition in include/ptamd.h; PARITY UNPINNED like the Kabsch RMSD above).
 """
 import numpy as np
 import torch
@@ -50,6 +54,26 @@ def lddt_batch(pred_crd, true_crd, seq, cutoff=15.0):
                                _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "lddt")
     return score, per_res, counts
+
+
+def tm_batch(pred_crd, true_crd, seq):
+    """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] ->
+    (score [B,3] = {tm, gdt_ts, gdt_ha}, counts [B,6] int32 = {N, c0.5, c1, c2, c4, c8}, xform [B,3,4] = (R | t) with
+    R p + t on q), all on the device, no sync: TM-score and GDT over the C-alphas, maximised by the seed-and-refine search of
+    csrc/tmscore.hip (definition in include/ptamd.h).  NaN = fewer than 3 present C-alphas or a non-finite prediction on one."""
+    _lib.require_gpu(pred_crd, true_crd, seq)
+    B, L = seq.shape
+    assert pred_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crd.shape == pred_crd.shape
+    dev = seq.device
+    score = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(B, 6, dtype=torch.int32, device=dev)
+    xform = torch.empty(B, 12, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("tm", _lib.lib().ptamd_tm_workspace_bytes(B, L), dev)
+    rc = _lib.lib().ptamd_tm_score(_lib.ptr(pred_crd.float().contiguous()), _lib.ptr(true_crd.float().contiguous()),
+                                   _lib.ptr(seq.contiguous()), B, L, _lib.ptr(score), _lib.ptr(counts), _lib.ptr(xform),
+                                   _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "tm_score")
+    return score, counts, torch.cat([xform[:, :9].reshape(B, 3, 3), xform[:, 9:].reshape(B, 3, 1)], dim=2)
 
 
 def clash_batch(crd, seq, tolerance=1.5):
@@ -95,3 +119,15 @@ def batch_lddt(pred_sincos, true_crds, input_seqs, cutoff=15.0):
     crd, _ = nerf_forward(ang, input_seqs)
     s = finite_sums(lddt_batch(crd, true_crds, input_seqs, cutoff)[0]).cpu().numpy()
     return tuple(float(s[k] / s[2 + k]) if s[2 + k] > 0 else float("nan") for k in range(2))
+
+
+def batch_tm(pred_sincos, true_crds, input_seqs):
+    """(tm, gdt_ts, gdt_ha): means over the proteins with a finite score of the TM-score and GDT of the structures built from
+    pred_sincos (NaN when no protein has one); one host read."""
+    from .losses import angles_forward, finite_sums
+    from .protein.Structure import nerf_forward
+    B, L = input_seqs.shape
+    ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
+    crd, _ = nerf_forward(ang, input_seqs)
+    s = finite_sums(tm_batch(crd, true_crds, input_seqs)[0]).cpu().numpy()
+    return tuple(float(s[k] / s[3 + k]) if s[3 + k] > 0 else float("nan") for k in range(3))

@@ -25,7 +25,9 @@ _HISTORY = ("drmsd", "combined", "lndrmsd", "mse")
 _LDDT = ("lddt-full", "lddt-ca")
 # `train.py --eval_clash` (evaluation) and `--clash_weight` (every step): the steric clash term, kept exactly like the lDDT pair
 _CLASH = ("clash-full",)
-_OPTIONAL = _LDDT + _CLASH
+# `train.py --eval_tm` (evaluation only): TM-score and GDT_TS / GDT_HA over the C-alphas, kept like the lDDT pair
+_TM = ("tm-ca", "gdt-ts", "gdt-ha")
+_OPTIONAL = _LDDT + _CLASH + _TM
 # `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
 # above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
 # exactly their keys
@@ -151,19 +153,21 @@ REFERENCE_CSV = False     # True: the granularity column carries upstream's lite
 def prepare_log_header(args):
     tail = ',lddt,lddt_ca' if getattr(args, "eval_lddt", False) else ''      # two trailing columns under --eval_lddt only
     tail += ',clash' if getattr(args, "eval_clash", False) else ''            # one more, behind them, under --eval_clash only
+    tail += ',tm,gdt_ts,gdt_ha' if getattr(args, "eval_tm", False) else ''    # three more, behind those, under --eval_tm only
     if args.loss == "combined":
         return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed' + tail
     return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed' + tail
 
 
-def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False):
+def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False, tm=False):
     """One CSV row (log.py:115-130): ten values - drmsd, ln_drmsd, rmse, rmsd, combined, lr, mode, granularity, time,
     speed; like upstream the `combined` value is written whatever the header of `prepare_log_header` lists.  One
     deliberate difference: the granularity column says "batch" for per-batch rows (upstream writes the literal "epoch"
     in both cases, log.py:130) - unless `REFERENCE_CSV` is set (`train.py --reference-csv`), which reproduces the
     upstream column byte for byte for consumers of the reference's `.train` files.  `lddt` (`train.py --eval_lddt`): two
     trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it).  `clash`
-    (`train.py --eval_clash`): one more trailing value, the epoch's clash-full, nan on rows that have none."""
+    (`train.py --eval_clash`): one more trailing value, the epoch's clash-full, nan on rows that have none.  `tm`
+    (`train.py --eval_tm`): three more, the epoch's tm-ca, gdt-ts and gdt-ha, nan on rows that have none."""
     t = t or time.time()
     m = metrics[mode]
     be = "epoch" if end_of_epoch else "batch"
@@ -176,6 +180,8 @@ def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False,
         row += [m.get(f"{be}-{k}", float("nan")) for k in _LDDT]
     if clash:
         row += [m.get(f"{be}-{k}", float("nan")) for k in _CLASH]
+    if tm:
+        row += [m.get(f"{be}-{k}", float("nan")) for k in _TM]
     log_writer.writerow(row)
 
 
@@ -188,7 +194,7 @@ def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer
     metrics["history-lr"].append(lr)
     if dp.is_main():
         log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)),
-                  clash=bool(getattr(args, "eval_clash", False)))
+                  clash=bool(getattr(args, "eval_clash", False)), tm=bool(getattr(args, "eval_tm", False)))
         if step % max(1, getattr(args, "log_wandb_step", 1) * 10) == 0:
             m = metrics["train"]
             print(f"  step {step:5d}  drmsd {m['batch-drmsd-full']:.4f}  ln {m['batch-lndrmsd-full']:.6f}  "
@@ -232,6 +238,6 @@ def do_eval_epoch_logging(metrics, mode):
     update_metrics_end_of_epoch(metrics, mode)
     if dp.is_main():
         m = metrics[mode]
-        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _OPTIONAL if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash only
+        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _OPTIONAL if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash, --eval_tm only
         print(f"  [{mode}] drmsd {m['epoch-drmsd-full']:.4f}  ln {m['epoch-lndrmsd-full']:.6f}  "
               f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}{tail}", flush=True)

@@ -427,7 +427,7 @@ def _local_layout(B, present):
 # None for a rank that has no value}; every rank of a job asks for the same fields, a rank with an empty shard included, so their
 # vectors have one length).  A report nobody asked a tail of has exactly the layout, the keys and the size it had before there
 # was one.  field -> the `wait()` keys of its columns:
-_TAIL_FIELDS = {"clash": ("clash",)}
+_TAIL_FIELDS = {"clash": ("clash",), "tm": ("tm-ca", "gdt-ts", "gdt-ha")}
 
 
 def _tail_layout(tail, start, width):
@@ -555,15 +555,18 @@ class LossReport:
     """
 
     def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, clash=None, with_clash=False,
-                 lddt=None, slddt=None, fape=None):
+                 tm=None, with_tm=False, lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
         `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None.
         `clash`: the per-protein clash losses [B] (`--clash_weight`, `--eval_clash`) or None; `with_clash`: the job reports them -
         true on EVERY rank then, also on one whose shard is empty and has none: the report carries the tail for them, and `wait()`
-        the key `clash`."""
+        the key `clash`.
+        `tm`: the per-protein scores [B,3] of eval_metrics.tm_batch (evaluation under --eval_tm) or None; `with_tm` as `with_clash`:
+        one more tail field of three columns, and `wait()` the keys `tm-ca`, `gdt-ts`, `gdt-ha`."""
         self.world, self.n_res = dp.world_size(), n_res
         channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
-        tail = {"clash": clash} if with_clash or clash is not None else None
+        tail = {**({"clash": clash} if with_clash or clash is not None else {}),
+                **({"tm": tm} if with_tm or tm is not None else {})} or None
         if self.world == 1:
             buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
                                      alloc=lambda n: _pinned("report32", n, torch.float32, device), tail=tail)

@@ -138,6 +138,12 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     of the GLOBAL batch that have a finite one.  Refused with `args.backbone_loss` and with `-l mse`.  `args.eval_clash`: in
     `eval_mode` the key `clash-full` is reported also when W = 0, from the coordinates already built.  With neither, nothing is
     computed and the key is absent.
+
+    `args.eval_tm` (eval_metrics.tm_batch; Zhang & Skolnick's TM-score and the GDT counts of the same superposition search; not in
+    the reference): in `eval_mode` the dictionary gains `tm-ca`, `gdt-ts` and `gdt-ha`, each the mean over the proteins of the
+    GLOBAL batch that have a finite score, from the coordinates evaluation has already built (all atoms, also under
+    `args.backbone_loss` and `args.rename_symmetric`).  Without the flag, and in every training step - where, under `-l mse`, no
+    structure exists - nothing is computed and the keys are absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
@@ -147,6 +153,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     if extra is not None and backbone:
         raise ValueError(extra.backbone_message)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
+    want_tm = eval_mode and bool(getattr(args, "eval_tm", False))
     rename = bool(getattr(args, "rename_symmetric", False))
     if rename and (backbone or not need_drmsd):
         raise ValueError(RENAME_BACKBONE_MESSAGE if backbone else RENAME_NO_STRUCTURE_MESSAGE)
@@ -155,7 +162,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         raise ValueError(CLASH_BACKBONE_MESSAGE if backbone else CLASH_NO_STRUCTURE_MESSAGE)
     want_clash = clash_w > 0 or (eval_mode and bool(getattr(args, "eval_clash", False)))
     ckw = {"clash": (clash_w, clash_tol)} if clash_w > 0 else {}      # (the term trains: batch_loss runs it on the gradient's way)
-    sums = stats = grad = status = rmsd = lddt = per_protein = clash = None
+    sums = stats = grad = status = rmsd = lddt = per_protein = clash = tm = crd = None
     if not empty and rename:
         # the structure and the renaming come first: the MSE, the RMSD and the lDDT below see the renamed truth
         res = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True, rename_symmetric=True,
@@ -202,9 +209,13 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     if want_clash and not empty and clash is None:         # --eval_clash without the training term: on the coordinates already built
         from .eval_metrics import clash_batch
         clash = clash_batch(crd, src_seq, clash_tol)[0]
+    if want_tm and not empty:
+        from .eval_metrics import tm_batch                 # evaluation always builds every atom: on those coordinates
+        tm = tm_batch(crd, tgt_crds, src_seq)[0]           # (--rename_symmetric renames side-chain atoms: the C-alphas are the same)
     report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
                         **({extra.name: per_protein} if extra is not None else {}),
-                        **({"clash": clash, "with_clash": True} if want_clash else {}))
+                        **({"clash": clash, "with_clash": True} if want_clash else {}),
+                        **({"tm": tm, "with_tm": True} if want_tm else {}))
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -251,6 +262,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             out["loss"] = loss + clash_w * out["clash-full"]
     if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
         out["lddt-full"], out["lddt-ca"] = channel("lddt"), channel("lddt-ca")
+    if want_tm:         # --eval_tm: three more keys, means over the proteins of the GLOBAL batch that have a score
+        out["tm-ca"], out["gdt-ts"], out["gdt-ha"] = channel("tm-ca"), channel("gdt-ts"), channel("gdt-ha")
     if host["n_res"] is not None:
         out["n-residues"] = host["n_res"]                      # residues of the GLOBAL batch (speed meter, log.py)
     return out
@@ -283,14 +296,14 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
             metrics = eval_epoch(model, train_eval_loader, device, args, metrics, mode="train", pool=drmsd_worker_pool)
         if dp.is_main():
             log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False))
+                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
         if not args.train_only:
             for split, validation_data in validation_datasets.items():
                 metrics = eval_epoch(model, validation_data, device, args, metrics, mode=f"valid-{split}",
                                      pool=drmsd_worker_pool)
                 if dp.is_main():
                     log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False))
+                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
         # every rank holds the same (globally reduced) metrics, so the scheduler, the early-stopping test and the
         # checkpoint policy below take the same branch on every rank
         if scheduler:
@@ -305,7 +318,7 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
         metrics = eval_epoch(model, test_data, device, args, metrics, mode="test", pool=drmsd_worker_pool)
         if dp.is_main():
             log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False))
+                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
     return metrics
 
 
@@ -660,6 +673,10 @@ def create_parser():
     new.add_argument("--eval_clash", action="store_true",
                      help="evaluation also reports the steric clash term of the predicted structures: one more value on the "
                           "per-epoch evaluation line, one trailing column in the .train log")
+    new.add_argument("--eval_tm", action="store_true",
+                     help="evaluation also reports TM-score and GDT_TS / GDT_HA over the C-alphas (the superposition search of the "
+                          "TMscore program, on the device): three more values on the per-epoch evaluation line, three trailing "
+                          "columns in the .train log")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
