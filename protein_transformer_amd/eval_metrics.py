@@ -101,33 +101,31 @@ def rmsd(a, b):
 
 def batch_rmsd(pred_sincos, true_crds, input_seqs):
     """np.mean over proteins of the superposed RMSD of the structures built from pred_sincos (one host read)."""
-    from .losses import angles_forward
-    from .protein.Structure import nerf_forward
-    B, L = input_seqs.shape
-    ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
-    crd, _ = nerf_forward(ang, input_seqs)
+    from .losses import predicted_coords
+    crd, _ = predicted_coords(pred_sincos, input_seqs)
     return float(kabsch_rmsd_batch(crd, true_crds, input_seqs).double().mean())
+
+
+def _finite_means(scores):
+    """scores [B,k] (device) -> k host floats: per column the mean over the proteins with a finite score, NaN when none has one;
+    one host read."""
+    from .losses import finite_sums
+    k = scores.shape[1]
+    s = finite_sums(scores).cpu().numpy()
+    return tuple(float(s[j] / s[k + j]) if s[k + j] > 0 else float("nan") for j in range(k))
 
 
 def batch_lddt(pred_sincos, true_crds, input_seqs, cutoff=15.0):
     """(lddt-full, lddt-ca): means over the proteins with a finite score of the lDDT of the structures built from
     pred_sincos (NaN when no protein has one); one host read."""
-    from .losses import angles_forward, finite_sums
-    from .protein.Structure import nerf_forward
-    B, L = input_seqs.shape
-    ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
-    crd, _ = nerf_forward(ang, input_seqs)
-    s = finite_sums(lddt_batch(crd, true_crds, input_seqs, cutoff)[0]).cpu().numpy()
-    return tuple(float(s[k] / s[2 + k]) if s[2 + k] > 0 else float("nan") for k in range(2))
+    from .losses import predicted_coords
+    crd, _ = predicted_coords(pred_sincos, input_seqs)
+    return _finite_means(lddt_batch(crd, true_crds, input_seqs, cutoff)[0])
 
 
 def batch_tm(pred_sincos, true_crds, input_seqs):
     """(tm, gdt_ts, gdt_ha): means over the proteins with a finite score of the TM-score and GDT of the structures built from
     pred_sincos (NaN when no protein has one); one host read."""
-    from .losses import angles_forward, finite_sums
-    from .protein.Structure import nerf_forward
-    B, L = input_seqs.shape
-    ang = angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1))
-    crd, _ = nerf_forward(ang, input_seqs)
-    s = finite_sums(tm_batch(crd, true_crds, input_seqs)[0]).cpu().numpy()
-    return tuple(float(s[k] / s[3 + k]) if s[3 + k] > 0 else float("nan") for k in range(3))
+    from .losses import predicted_coords
+    crd, _ = predicted_coords(pred_sincos, input_seqs)
+    return _finite_means(tm_batch(crd, true_crds, input_seqs)[0])

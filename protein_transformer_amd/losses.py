@@ -210,11 +210,6 @@ def rename_symmetric(crd, true_crds, seq, true_ang=None):
     return crd_out, ang_out, swapped, cost
 
 
-# batch_loss's keyword `rename_symmetric` (the name the command line and the callers use) hides the function inside batch_loss:
-# this alias is how batch_loss, and nobody else, reaches it
-_rename_truth = rename_symmetric
-
-
 # ----------------------------------------------------------------------------- the extra structural losses
 # All the host code knows about a structural loss beside the dRMSD family (`train.py -l <name>`; the name is also its keyword in
 # `batch_loss` and `LossReport` and its key in `LossReport.wait()`).  run(crd, true_crds, seq, need_grad, params) -> (per-protein
@@ -308,36 +303,39 @@ def angles_to_coords(angles, seq, remove_batch_padding=False):
     return generate_coords(angles, seq)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=False, backbone_only=False, slddt=None, fape=None,
-               clash=None, rename_symmetric=False, true_ang=None):
-    """Device-resident core of compute_batch_drmsd: no host synchronisation.
+def predicted_coords(pred_sincos, seqs, status=None, backbone_only=False):
+    """Every atom ([B,L*14,3]; `backbone_only`: N, CA, C as the compact [B,L*3,3]) of the structures that the predictions
+    pred_sincos [B,L,24] (cos, sin) stand for, as a constant: (crd, status word - `status` itself when one is passed).  No sync."""
+    B, L = seqs.shape
+    return nerf_forward(angles_forward(pred_sincos.detach().float().contiguous().view(B, L, -1)), seqs, status=status,
+                        backbone_only=backbone_only)
 
-    Returns (stats [B,8] device tensor, d(sum_i lndrmsd_i)/d(pred_sincos) or None, status int32[1]) and, with
-    `return_crd`, the predicted coordinates [B, L*14, 3] as a fourth value.
 
-    `backbone_only` (losses.py:83-92, --backbone_loss): the loss over N, CA, C alone - the backbone chain kernels without the
-    side-chain builder, the pair sweep over 3 L atoms per protein.  stats[:, 2], [:, 3], [:, 5] (mirrored in [:, 0], [:, 1],
-    [:, 4]) are the backbone numbers of the full call, the gradient is d(sum_i lndrmsd-bb_i)/d(pred_sincos) - exactly zero in the
-    side-chain channels - and the coordinates of `return_crd` are the compact [B, L*3, 3] backbone.
+BatchLoss = namedtuple("BatchLoss", "stats grad status crd per_protein true_crds true_ang clash", defaults=(None,) * 8)
+_renamed_truth = rename_symmetric            # (batch_loss has a keyword of the function's name)
 
-    An extra loss (EXTRA_LOSSES: one keyword each, at most one given; None: everything above is unchanged): the structure is
-    trained on that loss instead - angles -> NeRF forward -> the loss -> NeRF adjoint -> angles adjoint.  The gradient is
-    d(sum_i loss_i)/d(pred_sincos), `stats` are still the dRMSD statistics (taken forward-only on the same coordinates, so logs stay
-    comparable between runs), and the per-protein losses [B] (NaN for a protein without one) are appended as the last value.
-      `slddt` = (cutoff, temperature): the smooth lDDT loss of csrc/slddt.hip (`train.py -l slddt`).
-      `fape` = clamp in Angstrom: the frame aligned point error of csrc/fape.hip (`train.py -l fape`).
 
-    `rename_symmetric` (`train.py --rename_symmetric`; off: nothing above changes and nothing more is launched): the truth is
-    renamed once, against the coordinates just built (`rename_symmetric` above) - the dRMSD statistics, the extra loss and all
-    gradients use the renamed truth, which is a constant for the gradient.  The renamed truth [B,L*14,3] and the renamed `true_ang`
-    ([B,L,24]; None when `true_ang` was not given) are appended behind everything else, for the caller's RMSD, lDDT and MSE.
-    Refused together with `backbone_only`: no side chains are built there.
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, backbone_only=False, slddt=None, fape=None, clash=None,
+               rename_symmetric=False, true_ang=None):
+    """Device-resident core of compute_batch_drmsd: angles -> NeRF forward -> the loss -> NeRF adjoint -> angles adjoint, no host
+    synchronisation.  Returns a BatchLoss; a field nobody asked for is None:
 
-    `clash` = (weight, tolerance) (`train.py --clash_weight`, `--clash_tolerance`; None: nothing above changes and nothing more is
-    launched): the steric clash term of csrc/clash.hip joins whichever loss trains the structure.  Its kernel runs after that loss
-    has produced the coordinate gradient and adds weight * d(sum_i clash_i) to it in place, so the one NeRF adjoint carries both
-    terms: the gradient is d(sum_i loss_i + weight * sum_i clash_i)/d(pred_sincos).  The per-protein clash losses [B] (unweighted;
-    NaN for a protein without one) are appended as the very last value.  Refused together with `backbone_only`.
+    stats        [B,8], the dRMSD statistics.  `backbone_only` (losses.py:83-92, --backbone_loss; the backbone chain kernels and a
+                 pair sweep over 3 L atoms, no side chains): [:, 2], [:, 3], [:, 5] of the full call, mirrored in [:, :2], [:, 4].
+    grad         with `do_backward`, d(sum_i loss_i)/d(pred_sincos) [B,L,24]: loss_i is lndrmsd_i, lndrmsd-bb_i under `backbone_only`
+                 (exactly zero in the side-chain channels), or the extra loss (`stats` is then forward-only, on the same build).
+    status       int32[1], the status word of the build.
+    crd          the coordinates that were built, [B,L*14,3]; the compact [B,L*3,3] backbone under `backbone_only`.
+    per_protein  [B] (NaN: the protein has none), the extra loss that trains the structure instead of the dRMSD (EXTRA_LOSSES, at
+                 most one): `slddt` = (cutoff, temperature), csrc/slddt.hip; `fape` = clamp in Angstrom, csrc/fape.hip.
+    true_crds,   the truth every number above was taken against and every caller's RMSD, lDDT and MSE should be: the arguments as
+    true_ang     passed, or with `rename_symmetric` the tensors renamed once against `crd` (`rename_symmetric` above; a constant for
+                 the gradient; true_ang None when it was not given).
+    clash        [B] (unweighted; NaN: none), with `clash` = (weight, tolerance): the clash term of csrc/clash.hip joins the loss.
+                 Its kernel adds weight * d(sum_i clash_i) to the coordinate gradient in place, in front of the one NeRF adjoint.
+
+    The extra losses, `rename_symmetric` and `clash` need side chains and are refused together with `backbone_only`; whatever is
+    not asked for launches nothing.
     """
     given = [(EXTRA_LOSSES[name], params) for name, params in (("slddt", slddt), ("fape", fape)) if params is not None]
     assert len(given) <= 1, "one structural loss at a time"
@@ -350,24 +348,20 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, return_crd=
     sc = pred_sincos.view(B, L, NUM_PREDICTED_ANGLES * 2)
     ang = angles_forward(sc)
     crd, status = nerf_forward(ang, input_seqs, backbone_only=backbone_only)
-    renamed = ()
     if rename_symmetric:
-        true_crds, true_ang = _rename_truth(crd, true_crds, input_seqs, true_ang)[:2]
-        renamed = (true_crds, true_ang)
+        true_crds, true_ang = _renamed_truth(crd, true_crds, input_seqs, true_ang)[:2]
     stats, dcrd = drmsd_forward_backward(crd, true_crds.float(), input_seqs, need_grad=do_backward and extra is None,
                                          backbone_only=backbone_only)
+    per_protein = clashes = grad = None
     if extra is not None:
         per_protein, dcrd = extra.run(crd, true_crds, input_seqs, do_backward, params)
-    clashes = ()
     if clash is not None:
-        clashes = (clash_forward_backward(crd, input_seqs, need_grad=do_backward, tolerance=clash[1], weight=clash[0],
-                                          accumulate_into=dcrd if do_backward else None)[0][:, 0],)
-    grad = None
+        clashes = clash_forward_backward(crd, input_seqs, need_grad=do_backward, tolerance=clash[1], weight=clash[0],
+                                         accumulate_into=dcrd if do_backward else None)[0][:, 0]
     if do_backward:
         dang = nerf_backward(ang, input_seqs, crd, dcrd, backbone_only=backbone_only)
         grad = angles_backward(sc, dang)
-    out = (stats, grad, status, crd) if return_crd else (stats, grad, status)
-    return (out if extra is None else out + (per_protein,)) + renamed + clashes
+    return BatchLoss(stats, grad, status, crd, per_protein, true_crds, true_ang, clashes)
 
 
 # ----------------------------------------------------------------------------- statistics hand-over
@@ -604,14 +598,12 @@ def compute_batch_drmsd(pred_angs, true_crds, input_seqs, device=None, return_rm
     """
     dev = pred_angs.device
     true_crds, input_seqs = true_crds.to(dev), input_seqs.to(dev)
-    stats, grad, status, crd = batch_loss(pred_angs, true_crds, input_seqs, do_backward, return_crd=True,
-                                          backbone_only=backbone_only)
+    stats, grad, status, crd = batch_loss(pred_angs, true_crds, input_seqs, do_backward, backbone_only=backbone_only)[:4]
     rmsd = None
     if return_rmsd:
         from .eval_metrics import kabsch_rmsd_batch
         if backbone_only:
-            crd, _ = nerf_forward(angles_forward(pred_angs.detach().float().contiguous().view(*input_seqs.shape, -1)), input_seqs,
-                                  status=status)
+            crd, _ = predicted_coords(pred_angs, input_seqs, status=status)
         rmsd = kabsch_rmsd_batch(crd, true_crds, input_seqs)
     # The copy to the host is enqueued right behind the loss kernels and the host waits for THAT copy only after the
     # whole backward pass has been enqueued: waiting on the stream instead would drain the queue at the end of every

@@ -25,11 +25,13 @@ import torch
 
 from . import dp
 from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
+from .eval_metrics import clash_batch, kabsch_rmsd_batch, lddt_batch, tm_batch
 from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging,
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
 from .losses import (CLASH_BACKBONE_MESSAGE, CLASH_NO_STRUCTURE_MESSAGE, CLASH_TOLERANCE, EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE,
-                     RENAME_NO_STRUCTURE_MESSAGE, LossReport, batch_loss, clash_check, combine_drmsd_mse, mse_grad, mse_sums)
+                     RENAME_NO_STRUCTURE_MESSAGE, BatchLoss, LossReport, batch_loss, clash_check, combine_drmsd_mse, mse_grad,
+                     mse_sums, predicted_coords)
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
 from .optim import FusedAdam, FusedSGD, ScheduledOptim
@@ -129,7 +131,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     `args.rename_symmetric` (losses.rename_symmetric; not in the reference): the structure is built first and the truth - coordinates
     and angles - renamed against it at its symmetric side chains (ASP, GLU, PHE, TYR); every number above, every gradient, the MSE,
     `rmsd-full` and the lDDT are then taken against the renamed truth.  No key is added.  Refused with `args.backbone_loss` and
-    wherever no structure is built (a training step of `-l mse`).  Without the flag, order and calls are what they were.
+    wherever no structure is built (a training step of `-l mse`).  Without the flag nothing more is launched.
 
     `args.clash_weight` W > 0, `args.clash_tolerance` (losses.clash_forward_backward; AlphaFold 2's between-residue violation term;
     not in the reference): the steric clash term joins whichever structural loss trains the structure.  The injected gradient gains
@@ -161,59 +163,36 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     if clash_w > 0 and (backbone or not need_drmsd):
         raise ValueError(CLASH_BACKBONE_MESSAGE if backbone else CLASH_NO_STRUCTURE_MESSAGE)
     want_clash = clash_w > 0 or (eval_mode and bool(getattr(args, "eval_clash", False)))
-    ckw = {"clash": (clash_w, clash_tol)} if clash_w > 0 else {}      # (the term trains: batch_loss runs it on the gradient's way)
-    sums = stats = grad = status = rmsd = lddt = per_protein = clash = tm = crd = None
-    if not empty and rename:
-        # the structure and the renaming come first: the MSE, the RMSD and the lDDT below see the renamed truth
-        res = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, return_crd=True, rename_symmetric=True,
-                         true_ang=tgt_ang, **({extra.name: extra.params(args)} if extra is not None else {}), **ckw)
-        if ckw:
-            *res, clash = res
-        *head, tgt_crds, tgt_ang = res
-        stats, grad, status, crd = head[:4]
-        per_protein = head[4] if extra is not None else None
-        sums = mse_sums(pred, tgt_ang)
-        if return_rmsd:
-            from .eval_metrics import kabsch_rmsd_batch
+    structure = need_drmsd and not empty
+    compact = backbone and not eval_mode       # a training step under --backbone_loss builds no side chains: N, CA, C alone
+    res = BatchLoss()
+    grad = sums = rmsd = lddt = clash = tm = None
+    if structure:
+        # the structure (and the renaming) come first: the MSE, the RMSD and the lDDT below see the truth the losses saw
+        kw = dict(do_backward=do_backwards and (compact or not backbone), backbone_only=compact, rename_symmetric=rename,
+                  true_ang=tgt_ang)
+        if extra is not None:                  # one build: dRMSD statistics forward-only, loss (and gradient) of the extra loss
+            kw[extra.name] = extra.params(args)
+        if clash_w > 0:                        # the term trains: batch_loss runs it on the gradient's way
+            kw["clash"] = (clash_w, clash_tol)
+        res = batch_loss(pred, tgt_crds, src_seq, **kw)
+        grad, clash, tgt_crds, tgt_ang = res.grad, res.clash, res.true_crds, res.true_ang
+        if backbone and not compact and do_backwards:      # evaluation that also back-propagates: the gradient is the backbone's
+            grad = batch_loss(pred, tgt_crds, src_seq, do_backward=True, backbone_only=True).grad
+    if not empty:
+        sums = mse_sums(pred, tgt_ang)                     # the three MSEs of train.py:64-66 in one pass
+    if structure:                              # evaluation has built every atom: its metrics need no second NeRF build
+        if return_rmsd:                        # (the compact backbone of a training step does: all atoms, for the RMSD alone)
+            crd = predicted_coords(pred, src_seq, status=res.status)[0] if compact else res.crd
             rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
         if want_lddt:
-            from .eval_metrics import lddt_batch
-            lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
-    elif not empty:
-        sums = mse_sums(pred, tgt_ang)                         # the three MSEs of train.py:64-66 in one pass
-        if need_drmsd:
-            if extra is not None:      # one build: dRMSD statistics forward-only, loss (and gradient) of the extra loss
-                stats, grad, status, crd, per_protein, *rest = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards,
-                                                                          return_crd=True, **{extra.name: extra.params(args)}, **ckw)
-                clash = rest[0] if ckw else None
-            elif backbone and not eval_mode:
-                stats, grad, status = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards, backbone_only=True)
-                crd = None
-            else:
-                stats, grad, status, crd, *rest = batch_loss(pred, tgt_crds, src_seq, do_backward=do_backwards and not backbone,
-                                                             return_crd=True, **ckw)
-                clash = rest[0] if ckw else None
-                if backbone and do_backwards:              # evaluation that also back-propagates: the gradient is the backbone's
-                    grad = batch_loss(pred, tgt_crds, src_seq, do_backward=True, backbone_only=True)[1]
-            if return_rmsd:
-                from .eval_metrics import kabsch_rmsd_batch
-                if crd is None:                            # all atoms, for the RMSD alone
-                    from .losses import angles_forward
-                    from .protein.Structure import nerf_forward
-                    crd, _ = nerf_forward(angles_forward(pred.detach().float().contiguous().view(*src_seq.shape, -1)), src_seq,
-                                          status=status)
-                rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
-            if want_lddt:                                  # on the coordinates evaluation has already built: no second NeRF build
-                from .eval_metrics import lddt_batch
-                lddt = lddt_batch(crd, tgt_crds, src_seq)[0]
-    if want_clash and not empty and clash is None:         # --eval_clash without the training term: on the coordinates already built
-        from .eval_metrics import clash_batch
-        clash = clash_batch(crd, src_seq, clash_tol)[0]
-    if want_tm and not empty:
-        from .eval_metrics import tm_batch                 # evaluation always builds every atom: on those coordinates
-        tm = tm_batch(crd, tgt_crds, src_seq)[0]           # (--rename_symmetric renames side-chain atoms: the C-alphas are the same)
-    report = LossReport(dev, stats=stats, status=status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
-                        **({extra.name: per_protein} if extra is not None else {}),
+            lddt = lddt_batch(res.crd, tgt_crds, src_seq)[0]
+        if want_clash and clash is None:       # --eval_clash without the training term
+            clash = clash_batch(res.crd, src_seq, clash_tol)[0]
+        if want_tm:                            # (--rename_symmetric renames side-chain atoms: the C-alphas are the same)
+            tm = tm_batch(res.crd, tgt_crds, src_seq)[0]
+    report = LossReport(dev, stats=res.stats, status=res.status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
+                        **({extra.name: res.per_protein} if extra is not None else {}),
                         **({"clash": clash, "with_clash": True} if want_clash else {}),
                         **({"tm": tm, "with_tm": True} if want_tm else {}))
     if do_backwards and not empty:
@@ -286,6 +265,7 @@ def eval_epoch(model, validation_data, device, args, metrics, mode="valid", pool
 def train(model, metrics, training_data, train_eval_loader, validation_datasets, test_data, optimizer, device, args,
           log_writer, scheduler, drmsd_worker_pool):
     """ Model training control loop (train.py:138-186). """
+    columns = {k: getattr(args, f"eval_{k}", False) for k in ("lddt", "clash", "tm")}      # log_batch: the rows' trailing columns
     for epoch_i in range(START_EPOCH, args.epochs):
         if dp.is_main():
             print(f'[ Epoch {epoch_i} ]')
@@ -295,15 +275,13 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
         if args.eval_train:
             metrics = eval_epoch(model, train_eval_loader, device, args, metrics, mode="train", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
+            log_batch(log_writer, metrics, START_TIME, mode="train", end_of_epoch=True, **columns)
         if not args.train_only:
             for split, validation_data in validation_datasets.items():
                 metrics = eval_epoch(model, validation_data, device, args, metrics, mode=f"valid-{split}",
                                      pool=drmsd_worker_pool)
                 if dp.is_main():
-                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
+                    log_batch(log_writer, metrics, START_TIME, mode=f"valid-{split}", end_of_epoch=True, **columns)
         # every rank holds the same (globally reduced) metrics, so the scheduler, the early-stopping test and the
         # checkpoint policy below take the same branch on every rank
         if scheduler:
@@ -317,8 +295,7 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
     if not args.train_only and test_data is not None:
         metrics = eval_epoch(model, test_data, device, args, metrics, mode="test", pool=drmsd_worker_pool)
         if dp.is_main():
-            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, lddt=getattr(args, "eval_lddt", False),
-                      clash=getattr(args, "eval_clash", False), tm=getattr(args, "eval_tm", False))
+            log_batch(log_writer, metrics, START_TIME, mode="test", end_of_epoch=True, **columns)
     return metrics
 
 

@@ -176,8 +176,8 @@ def test_backbone_flag_trains_instead_of_raising(dev):
 def test_backbone_stats_vs_fp64_and_vs_full_call(dev, ragged):
     from protein_transformer_amd.losses import batch_loss
     sincos, seq, crd = (ragged[k].to(dev) for k in ("sincos", "seq", "crd"))
-    stats, _, status = batch_loss(sincos, crd, seq, do_backward=False, backbone_only=True)
-    full, _, status_full = batch_loss(sincos, crd, seq, do_backward=False)
+    stats, _, status = batch_loss(sincos, crd, seq, do_backward=False, backbone_only=True)[:3]
+    full, _, status_full = batch_loss(sincos, crd, seq, do_backward=False)[:3]
     assert int(status.item()) == 0 and int(status_full.item()) == 0
     stats, full = stats.cpu().numpy(), full.cpu().numpy()
     for b, (d, ln, n_bb) in enumerate(ragged["stats64"]):
@@ -248,7 +248,7 @@ def check_gradient(grad_dev, grad64, lens, what):
 def test_backbone_gradient_vs_fp64_autograd_ragged(dev, ragged):
     from protein_transformer_amd.losses import batch_loss
     sincos, seq, crd = (ragged[k].to(dev) for k in ("sincos", "seq", "crd"))
-    _, grad, status = batch_loss(sincos, crd, seq, do_backward=True, backbone_only=True)
+    _, grad, status = batch_loss(sincos, crd, seq, do_backward=True, backbone_only=True)[:3]
     assert int(status.item()) == 0
     ref = ragged["grad64"].reshape(len(RAGGED_LENS), 64, 24)
     assert check_gradient(grad.view(len(RAGGED_LENS), 64, 24), ref, RAGGED_LENS, "ragged") > 0
@@ -270,7 +270,7 @@ def test_backbone_gradient_full_size_slice(dev):
     start = batch["start_ang_rad"]
     sincos = torch.stack([torch.cos(start), torch.sin(start)], -1).reshape(B, L, 24)
     seq, crd = batch["seq"], batch["true_crd"]
-    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), seq.to(dev), backbone_only=True)
+    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), seq.to(dev), backbone_only=True)[:3]
     assert int(status.item()) == 0
     full = batch_loss(sincos.to(dev), crd.to(dev), seq.to(dev), do_backward=False)[0]
     assert torch.allclose(stats[:, 2], full[:, 2], rtol=1e-4, atol=0) and torch.allclose(stats[:, 3], full[:, 3], rtol=0, atol=1e-6)
@@ -281,7 +281,7 @@ def test_backbone_gradient_full_size_slice(dev):
     for b in range(4):
         assert st[b, 2] == approx(stats64[b][0], rel=1e-4) and st[b, 3] == approx(stats64[b][1], abs=1e-6)
     # a protein's loss and gradient do not depend on the batch it is computed in beyond rounding (tile cut by batch occupancy)
-    s4, g4, _ = batch_loss(sincos[sub].to(dev), crd[sub].to(dev), seq[sub].to(dev), backbone_only=True)
+    s4, g4, _ = batch_loss(sincos[sub].to(dev), crd[sub].to(dev), seq[sub].to(dev), backbone_only=True)[:3]
     assert torch.allclose(s4, stats[sub], rtol=2e-6, atol=0)
     assert check_gradient(grad.view(B, L, 24)[sub], grad64, [L] * 4, "32 x 512 slice") > 0
     assert check_gradient(g4.view(4, L, 24), grad64, [L] * 4, "4 x 512") > 0
@@ -294,14 +294,14 @@ def test_side_chain_channels_do_not_reach_the_backbone_loss(dev, ragged):
     ref = ragged["grad64"].reshape(-1, 24)
     dead = (ref == 0).all(dim=0)
     assert dead.any()
-    s1, g1, _ = batch_loss(sincos, crd, seq, backbone_only=True)
+    s1, g1, _ = batch_loss(sincos, crd, seq, backbone_only=True)[:3]
     s1, g1 = s1.clone(), g1.clone()
     moved = sincos.clone()
     gen = torch.Generator().manual_seed(1)
     noise = torch.randn(moved.shape, generator=gen).to(dev)
     moved[..., dead.to(dev)] = noise[..., dead.to(dev)]
     assert not torch.equal(moved, sincos)
-    s2, g2, _ = batch_loss(moved, crd, seq, backbone_only=True)
+    s2, g2, _ = batch_loss(moved, crd, seq, backbone_only=True)[:3]
     assert torch.equal(s1, s2) and torch.equal(g1, g2)
     # ... while the full-atom loss does see them
     f1 = batch_loss(sincos, crd, seq, do_backward=False)[0]
@@ -324,7 +324,7 @@ def test_proteins_without_a_backbone_pair(dev):
     crd = crd.view(4, 32 * 14, 3)
     start = batch["start_ang_rad"]
     sincos = torch.stack([torch.cos(start), torch.sin(start)], -1).reshape(4, 32, 24)
-    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), batch["seq"].to(dev), backbone_only=True)
+    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), batch["seq"].to(dev), backbone_only=True)[:3]
     assert int(status.item()) == 0
     stats, grad = stats.cpu(), grad.view(4, 32, 24).cpu()
     assert torch.isfinite(grad).all()
@@ -512,7 +512,7 @@ def test_backbone_step_is_bit_reproducible(dev):
         model.zero_grad()
         pred = model(seq, ang)
         out = get_losses(bb_args("drmsd", clip=None), pred, ang, crd, seq)
-        s, g, _ = batch_loss(pred, crd, seq, backbone_only=True)
+        s, g, _ = batch_loss(pred, crd, seq, backbone_only=True)[:3]
         runs.append((model.flat_parameters()[1].clone(), s.clone(), g.clone(), float(out["loss"])))
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][2], runs[1][2])
     assert runs[0][3] == runs[1][3]

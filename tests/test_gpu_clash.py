@@ -201,9 +201,11 @@ def test_gradient_down_to_the_angles_against_fp64_autograd():
     W = 0.5
     plain = batch_loss(sc, true.to(dev), sq, do_backward=True)
     out = batch_loss(sc, true.to(dev), sq, do_backward=True, clash=(W, R.TOLERANCE))
-    assert len(plain) == 3 and len(out) == 4 and int(out[2].item()) == 0
+    unset = lambda r: {f for f, v in r._asdict().items() if v is None}                # noqa: E731
+    assert unset(plain) == {"per_protein", "true_ang", "clash"} and unset(out) == {"per_protein", "true_ang"}
+    assert int(out.status.item()) == 0
     assert torch.equal(out[0], plain[0])                               # the dRMSD statistics do not know about the term
-    assert torch.equal(out[3], stats[:, 0])                            # the unweighted per-protein values, appended last
+    assert torch.equal(out.clash, stats[:, 0])                         # the unweighted per-protein values
     both = plain[1].cpu().numpy() + W * grad.reshape(plain[1].shape)
     print(f"batch_loss: rel-L2 of the joint gradient {R.rel_l2(out[1].cpu().numpy(), both):.2e}")
     assert R.rel_l2(out[1].cpu().numpy(), both) < 1e-3

@@ -76,7 +76,7 @@ def test_config2_step_vs_fp64_oracle(dev):
     model.zero_grad()
     pred = model(seq, ang)
     losses = get_losses(args, pred, ang, crd, seq)
-    stats_dev, _, _ = batch_loss(pred, crd, seq, do_backward=False)
+    stats_dev, _, _ = batch_loss(pred, crd, seq, do_backward=False)[:3]
     stats_dev = stats_dev.cpu().numpy()
     stats, ref = _fp64_step(model, 8, seq, crd)
     for b in range(B):

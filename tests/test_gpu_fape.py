@@ -226,8 +226,8 @@ def test_gradient_down_to_the_angles_against_fp64_autograd():
     free = [fape_reference(crd64[b].detach().numpy(), true[b], seq[b], float("inf")) for b in range(len(seq))]
     clamp = well_posed_clamp([r["d"] for r in free])
     out = batch_loss(sincos.to(dev), torch.from_numpy(true).to(dev), batch["seq"].to(dev), do_backward=True, fape=clamp)
-    assert len(out) == 4 and int(out[2].item()) == 0
-    grad, fa = out[1].cpu().numpy(), out[3].cpu().numpy()
+    assert {f for f, v in out._asdict().items() if v is None} == {"true_ang", "clash"} and int(out.status.item()) == 0
+    grad, fa = out.grad.cpu().numpy(), out.per_protein.cpu().numpy()
     total = 0
     for b in range(len(seq)):
         ref = fape_reference(crd64[b], true[b], seq[b], clamp)

@@ -234,7 +234,7 @@ def test_batch_loss_vs_oracle_ragged(dev):
     batch = synthetic.make_batch(lens, L_pad=64, seed=21, build_coords=build, frac_missing=0.1)
     ang, seq, crd = batch["start_ang_rad"], batch["seq"], batch["true_crd"]
     sincos = torch.stack([torch.cos(ang), torch.sin(ang)], -1).reshape(len(lens), 64, 24) * 0.9
-    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), seq.to(dev), do_backward=True)
+    stats, grad, status = batch_loss(sincos.to(dev), crd.to(dev), seq.to(dev), do_backward=True)[:3]
     assert int(status.item()) == 0
     stats = stats.cpu().numpy()
     for b in range(len(lens)):
@@ -248,6 +248,49 @@ def test_batch_loss_vs_oracle_ragged(dev):
         assert stats[b, 3] == approx(lnbb, abs=1e-6), b
         a.backward(gradient=g)
         assert rel_l2(grad[b].cpu().numpy(), sc.grad.numpy()) < 1e-3, b
+
+
+def test_batch_loss_result_fields_under_every_keyword_combination(dev):
+    """BatchLoss: under each legal combination of the keywords exactly the documented fields are set, with the documented shapes
+    and dtypes, and without `rename_symmetric` the truth comes back as the very objects that were passed."""
+    import itertools
+    from protein_transformer_amd.losses import BatchLoss, batch_loss
+    B, L = 2, 8
+    g = torch.Generator().manual_seed(5)
+    seq = torch.randint(0, 20, (B, L), generator=g)
+    seq[0, :4] = torch.tensor([2, 3, 4, 19])                        # (ASP, GLU, PHE, TYR: something to rename)
+    seq[1, 5:] = 20                                                 # one protein of 5 residues, padded
+    crd = torch.randn(B, L * 14, 3, generator=g) * 5
+    crd[0, [3, 30, 33]] = float("nan")                              # a few missing atoms
+    crd[1, 5 * 14:] = 0
+    ang = torch.randn(B, L, 24, generator=g)
+    ang[1, 5:] = 0
+    pred, seq, crd, ang = torch.randn(B, L, 24, generator=g).to(dev), seq.to(dev), crd.to(dev), ang.to(dev)
+    f32 = torch.float32
+    cases = [dict(backbone_only=True)] + [
+        dict(**loss, **clash, **rename) for loss, clash, rename in itertools.product(
+            ({}, dict(slddt=(15.0, 1.0)), dict(fape=10.0)), ({}, dict(clash=(0.5, 1.5))),
+            ({}, dict(rename_symmetric=True), dict(rename_symmetric=True, true_ang=ang), dict(true_ang=ang)))]
+    for kw, do_backward in itertools.product(cases, (True, False)):
+        res = batch_loss(pred, crd, seq, do_backward=do_backward, **kw)
+        want = {"stats": ((B, 8), f32), "status": ((1,), torch.int32), "true_crds": ((B, L * 14, 3), f32),
+                "crd": ((B, L * (3 if kw.get("backbone_only") else 14), 3), f32)}
+        if do_backward:
+            want["grad"] = ((B, L, 24), f32)
+        if "slddt" in kw or "fape" in kw:
+            want["per_protein"] = ((B,), f32)
+        if "true_ang" in kw:
+            want["true_ang"] = ((B, L, 24), f32)
+        if "clash" in kw:
+            want["clash"] = ((B,), f32)
+        assert type(res) is BatchLoss and res._fields == ("stats", "grad", "status", "crd", "per_protein", "true_crds", "true_ang",
+                                                          "clash")
+        got = {f: (tuple(v.shape), v.dtype) for f, v in res._asdict().items() if v is not None}
+        assert got == want, (kw, do_backward)
+        if kw.get("rename_symmetric"):
+            assert res.true_crds is not crd and res.true_ang is not ang
+        else:
+            assert res.true_crds is crd and res.true_ang is kw.get("true_ang")
 
 
 # --------------------------------------------------------------------------- full benchmark size
@@ -280,8 +323,8 @@ def test_full_size_properties(dev):
     q, _ = torch.linalg.qr(torch.randn(3, 3, dtype=torch.float64))
     moved = (true_crd.double() @ q.to(dev) + 7.5).float()
     sincos = torch.stack([torch.cos(batch["start_ang_rad"]), torch.sin(batch["start_ang_rad"])], -1).reshape(B, L, 24)
-    s1, g1, _ = batch_loss(sincos.to(dev), true_crd, seq)
-    s2, g2, _ = batch_loss(sincos.to(dev), moved, seq)
+    s1, g1, _ = batch_loss(sincos.to(dev), true_crd, seq)[:3]
+    s2, g2, _ = batch_loss(sincos.to(dev), moved, seq)[:3]
     assert torch.allclose(s1[:, :4], s2[:, :4], rtol=2e-4, atol=1e-6)
     # values and gradients against the vectorised fp64 oracle on a 4-protein slice
     sub = slice(0, 4)

@@ -260,7 +260,7 @@ def _run_draw(case, draw, regime="arbitrary", probe_only=0):
                 get_losses(args, pred, ang, crd, seq)
             finally:
                 K_.linear_bwd_input = real_linear_bwd_input
-            stats_dev, _, _ = batch_loss(pred.detach(), crd, seq, do_backward=False)
+            stats_dev, _, _ = batch_loss(pred.detach(), crd, seq, do_backward=False)[:3]
             stats_dev = stats_dev.cpu().numpy().astype(np.float64)
             p_np = pred.detach().cpu().numpy().astype(np.float64)
             rad_dev = angles_forward(pred.detach())

@@ -414,11 +414,14 @@ def test_losses_and_gradients_do_not_depend_on_the_labels_of_the_truth(loss):
     kw = {"slddt": (15.0, 1.0)} if loss == "slddt" else {"fape": 10.0} if loss == "fape" else {}
     a = PL.batch_loss(pred, crd, seq, rename_symmetric=True, true_ang=ang, **kw)
     b = PL.batch_loss(pred, crd2, seq, rename_symmetric=True, true_ang=ang2, **kw)
-    assert len(a) == (6 if kw else 5) and torch.equal(a[1], b[1])
-    assert same_bits(a[-2].cpu().numpy(), b[-2].cpu().numpy()) and same_bits(a[-1].cpu().numpy(), b[-1].cpu().numpy())
-    plain = PL.batch_loss(pred, a[-2], seq, **kw)
-    assert len(plain) == len(a) - 2 and torch.equal(plain[1], a[1]) and torch.equal(plain[0], a[0])
-    assert PL.batch_loss(pred, crd, seq, rename_symmetric=True, **kw)[-1] is None            # no angles given: None back
+    unset = lambda r: {f for f, v in r._asdict().items() if v is None}                       # noqa: E731
+    assert unset(a) == ({"clash"} if kw else {"clash", "per_protein"}) and torch.equal(a[1], b[1])
+    assert same_bits(a.true_crds.cpu().numpy(), b.true_crds.cpu().numpy())
+    assert same_bits(a.true_ang.cpu().numpy(), b.true_ang.cpu().numpy())
+    plain = PL.batch_loss(pred, a.true_crds, seq, **kw)
+    assert unset(plain) == unset(a) | {"true_ang"} and plain.true_crds is a.true_crds           # (nothing renamed: what was passed)
+    assert torch.equal(plain[1], a[1]) and torch.equal(plain[0], a[0])
+    assert PL.batch_loss(pred, crd, seq, rename_symmetric=True, **kw).true_ang is None       # no angles given: None back
     assert not torch.equal(PL.batch_loss(pred, crd, seq, **kw)[1], PL.batch_loss(pred, crd2, seq, **kw)[1])
 
 

@@ -245,8 +245,8 @@ def test_gradient_down_to_the_angles_against_fp64_autograd(tau):
     ang = batch["start_ang_rad"]
     sincos = (torch.stack([torch.cos(ang), torch.sin(ang)], -1).reshape(len(seq), -1, 24) * 0.9).float()
     out = batch_loss(sincos.to(dev), torch.from_numpy(true).to(dev), batch["seq"].to(dev), do_backward=True, slddt=(cutoff, tau))
-    assert len(out) == 4 and int(out[2].item()) == 0
-    grad, sl = out[1].cpu().numpy(), out[3].cpu().numpy()
+    assert {f for f, v in out._asdict().items() if v is None} == {"true_ang", "clash"} and int(out.status.item()) == 0
+    grad, sl = out.grad.cpu().numpy(), out.per_protein.cpu().numpy()
     sc64 = sincos.double().clone().requires_grad_()
     crd64 = batched.generate_coords_batched(olosses.inverse_trig_transform(sc64), batch["seq"], torch.float64)
     total = 0
