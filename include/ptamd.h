@@ -142,6 +142,36 @@ int ptamd_drmsd_bb_fwd_bwd_budget(const float *pred_bb, const float *true_crd, c
 int ptamd_kabsch_rmsd(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *rmsd,
                       void *stream);
 
+/* The superposed RMSD as a training loss, forward + analytic backward, for a whole batch (csrc/kabsch_loss.hip): `-l kabsch`.
+ * It stands beside rmsd (losses.py:281-286), which the reference - and ptamd_kabsch_rmsd above - only evaluate: the metric models
+ * are selected by, made trainable.  Like ptamd_fape_fwd_bwd and unlike every distance-based loss here it tells a structure from
+ * its mirror image: the superposition is over PROPER rotations, so a mirrored prediction has dRMSD 0 and a large loss here.
+ *   Atoms.  The present atoms of protein i are the slots of non-pad residues whose true coordinate has no NaN, as in
+ *   ptamd_kabsch_rmsd; what the prediction holds never decides presence.  Let their predicted coordinates be a_1..a_n, their true
+ *   ones b_1..b_n, abar and bbar the means, and R the proper rotation (det = +1) that minimises sum |R (a_k - abar) - (b_k - bbar)|^2.
+ *   Loss.  With the residual r_k = R (a_k - abar) - (b_k - bbar):  loss_i = sqrt(sum |r_k|^2 / n).
+ *   Gradient.  d(loss_i)/d(a_k) = R^T r_k / (n loss_i).  R is optimal, so it contributes no term; sum r_k = 0, so the centring
+ *   contributes none.  Every other slot - absent atoms, pad residues, slots beyond the sequence - gets exactly zero.
+ *   Edges.  loss_i = 0: every residual is 0, the gradient is exactly zero and nothing is divided; a prediction whose present atoms
+ *   equal the truth bit for bit gets R = 1 exactly, loss_i = 0 and an all-zero gradient.  n < 3: loss_i = NaN and a zero gradient
+ *   (the rotation is not determined).  A NaN or infinite predicted coordinate on a present atom: loss_i = NaN and a zero gradient
+ *   for that whole protein (the rule of ptamd_fape_fwd_bwd, found by ptamd_kabsch_rmsd's test on the sums of squares); finite
+ *   coordinates of any size are used as they are; the other proteins of the batch are untouched.  Where the two largest
+ *   eigenvalues of Horn's 4x4 matrix coincide (for instance n collinear atoms) R is not unique and the loss is not differentiable:
+ *   a set of measure zero, on which the call returns the loss and the gradient of one of the minimisers.
+ *   Batch.  The reported batch value is the mean over the proteins with a finite loss; the back-propagated quantity is the SUM
+ *   over proteins of loss_i, as for every structural loss here.
+ *   stats [B,2] out = {loss_i, n_i}; dcrd [B,L*14,3] out, or NULL for the forward-only form (no gradient work; the same bits in
+ *   stats).
+ * One workgroup per protein, one launch, no workspace: moments in fp64 relative to the protein's first present atom pair (a
+ * structure 1e3 A from the origin loses nothing to cancellation), Horn's closed-form rotation (csrc/tm_rotation.h), the loss from
+ * the residuals themselves under that R (not from a trace formula), results rounded to fp32 once.  No atomics and fixed-order
+ * sums: two runs give the same bits, and a protein's result does not depend on the batch around it.  B or L <= 0, L beyond
+ * INT_MAX / 28 (the bound of ptamd_lddt), or a NULL crd, true_crd, seq or stats: PTAMD_ERR_BAD_SHAPE, nothing is launched or
+ * written.  No getenv, no state between calls. */
+int ptamd_kabsch_loss_fwd_bwd(const float *crd, const float *true_crd, const int64_t *seq, int B, int L,
+                              float *stats /* [B,2] = {loss_i, n_i} */, float *dcrd /* [B,L*14,3] or NULL */, void *stream);
+
 /* lDDT, all-atom and C-alpha, for a whole batch (csrc/lddt.hip).  The reference has no counterpart - its evaluation stops at
  * dRMSD and the superposed RMSD; this is the score of Mariani, Biasini, Barbato & Schwede, "lDDT: a local superposition-free
  * score for comparing protein structures and models using distance difference tests", Bioinformatics 29(21):2722-2728 (2013),

@@ -126,6 +126,7 @@ SIGNATURES = {
     "ptamd_drmsd_bb_workspace_bytes_budget": (_sz, [_i, _i, _sz]),
     "ptamd_drmsd_bb_fwd_bwd_budget": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _sz, _sz, _p]),
     "ptamd_kabsch_rmsd": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "ptamd_kabsch_loss_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
     "ptamd_lddt_workspace_bytes": (_sz, [_i, _i]),
     "ptamd_lddt": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "ptamd_tm_workspace_bytes": (_sz, [_i, _i]),

@@ -131,6 +131,24 @@ def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
     return stats, npairs, nclamped, dcrd
 
 
+# ----------------------------------------------------------------------------- superposed RMSD as a loss
+def kabsch_forward_backward(crd, true_crds, seq, need_grad=True):
+    """RMSD after optimal superposition (proper rotations) of a batch, as a loss (csrc/kabsch_loss.hip; definition in
+    include/ptamd.h; the reference only evaluates it, losses.py:281-286).  crd, true_crds [B,L*14,3], seq [B,L].  Returns (stats
+    [B,2] = {loss_i, n_i}, d(loss_i)/d(crd) or None); a protein with fewer than 3 present atoms, or with a NaN / infinite predicted
+    coordinate on a present atom, has a NaN loss and a zero gradient.  One launch, no workspace, no host synchronisation."""
+    _lib.require_gpu(crd, true_crds, seq)
+    B, L = seq.shape
+    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
+    dcrd = torch.empty_like(crd) if need_grad else None
+    rc = _lib.lib().ptamd_kabsch_loss_fwd_bwd(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(seq), B, L, _lib.ptr(stats),
+                                              _lib.ptr(dcrd), _lib.stream())
+    _lib.check(rc, "kabsch_loss_fwd_bwd")
+    return stats, dcrd
+
+
 # ----------------------------------------------------------------------------- steric clashes
 CLASH_RADII = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}       # van der Waals radius by element, in Angstrom (include/ptamd.h)
 CLASH_TOLERANCE = 1.5                                           # AlphaFold 2's overlap tolerance, in Angstrom
@@ -227,6 +245,11 @@ def _run_fape(crd, true_crds, seq, need_grad, params):
     return stats[:, 0], dcrd
 
 
+def _run_kabsch(crd, true_crds, seq, need_grad, params):
+    stats, dcrd = kabsch_forward_backward(crd, true_crds, seq, need_grad=need_grad)
+    return stats[:, 0], dcrd
+
+
 EXTRA_LOSSES = {e.name: e for e in (
     ExtraLoss("slddt", _run_slddt, lambda a: (float(getattr(a, "slddt_cutoff", 15.0)), float(getattr(a, "slddt_temperature", 1.0))),
               lambda p: None if all(0 < x < np.inf for x in p) else "--slddt_cutoff and --slddt_temperature must be finite and positive",
@@ -236,6 +259,9 @@ EXTRA_LOSSES = {e.name: e for e in (
               lambda p: None if p > 0 else "--fape_clamp must be positive (inf = unclamped)",          # (NaN fails)
               "-l fape needs every atom: it cannot be combined with --backbone_loss "
               "(a backbone FAPE needs the compact backbone layout and does not exist here)"),
+    ExtraLoss("kabsch", _run_kabsch, lambda a: True, lambda p: None,                                   # (no parameters)
+              "-l kabsch is an all-atom loss: it cannot be combined with --backbone_loss "
+              "(a backbone or C-alpha superposition loss does not exist here)"),
 )}
 
 
@@ -315,8 +341,8 @@ BatchLoss = namedtuple("BatchLoss", "stats grad status crd per_protein true_crds
 _renamed_truth = rename_symmetric            # (batch_loss has a keyword of the function's name)
 
 
-def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, backbone_only=False, slddt=None, fape=None, clash=None,
-               rename_symmetric=False, true_ang=None):
+def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, backbone_only=False, slddt=None, fape=None, kabsch=None,
+               clash=None, rename_symmetric=False, true_ang=None):
     """Device-resident core of compute_batch_drmsd: angles -> NeRF forward -> the loss -> NeRF adjoint -> angles adjoint, no host
     synchronisation.  Returns a BatchLoss; a field nobody asked for is None:
 
@@ -327,7 +353,8 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, backbone_on
     status       int32[1], the status word of the build.
     crd          the coordinates that were built, [B,L*14,3]; the compact [B,L*3,3] backbone under `backbone_only`.
     per_protein  [B] (NaN: the protein has none), the extra loss that trains the structure instead of the dRMSD (EXTRA_LOSSES, at
-                 most one): `slddt` = (cutoff, temperature), csrc/slddt.hip; `fape` = clamp in Angstrom, csrc/fape.hip.
+                 most one): `slddt` = (cutoff, temperature), csrc/slddt.hip; `fape` = clamp in Angstrom, csrc/fape.hip;
+                 `kabsch` = True (it has no parameters), csrc/kabsch_loss.hip.
     true_crds,   the truth every number above was taken against and every caller's RMSD, lDDT and MSE should be: the arguments as
     true_ang     passed, or with `rename_symmetric` the tensors renamed once against `crd` (`rename_symmetric` above; a constant for
                  the gradient; true_ang None when it was not given).
@@ -337,7 +364,8 @@ def batch_loss(pred_sincos, true_crds, input_seqs, do_backward=True, backbone_on
     The extra losses, `rename_symmetric` and `clash` need side chains and are refused together with `backbone_only`; whatever is
     not asked for launches nothing.
     """
-    given = [(EXTRA_LOSSES[name], params) for name, params in (("slddt", slddt), ("fape", fape)) if params is not None]
+    asked = dict(slddt=slddt, fape=fape, kabsch=kabsch)
+    given = [(extra, asked[name]) for name, extra in EXTRA_LOSSES.items() if asked[name] is not None]
     assert len(given) <= 1, "one structural loss at a time"
     extra, params = given[0] if given else (None, None)
     assert extra is None or not backbone_only, extra.backbone_message
@@ -380,7 +408,9 @@ def _pinned(kind, n, dtype, device):
 
 # A CHANNEL of a report: per-protein fp32 values [B], reported as their mean over the proteins of the global batch that have a
 # finite one.  A field of k columns carries k channels (`lddt`, of --eval_lddt: two); field -> the `wait()` keys of its columns:
-_CHANNEL_FIELDS = {"lddt": ("lddt", "lddt-ca"), **{name: (name,) for name in EXTRA_LOSSES}}
+# These three are the fixed part of every report and of the reduced vector, whose slots stay where they have always been; an
+# extra loss that came later (`kabsch`) travels in the tail below.
+_CHANNEL_FIELDS = {"lddt": ("lddt", "lddt-ca"), "slddt": ("slddt",), "fape": ("fape",)}
 _MEANS = ("drmsd", "lndrmsd", "drmsd-bb", "lndrmsd-bb")        # stats[:, :4], reported as their means over the proteins
 _NO_REPORT = {**dict.fromkeys(_MEANS, 0.0), "rmsd": None, "n_proteins": 0, "status": 0, "n_res": None, "mse": None,
               **{key: None for keys in _CHANNEL_FIELDS.values() for key in keys}}
@@ -422,6 +452,10 @@ def _local_layout(B, present):
 # vectors have one length).  A report nobody asked a tail of has exactly the layout, the keys and the size it had before there
 # was one.  field -> the `wait()` keys of its columns:
 _TAIL_FIELDS = {"clash": ("clash",), "tm": ("tm-ca", "gdt-ts", "gdt-ha")}
+# ... and behind those the extra losses that have no channel in the fixed part (`kabsch`): one column each, asked for in the runs
+# whose loss it is (LossReport's keyword with_<name>)
+TAIL_LOSSES = tuple(name for name in EXTRA_LOSSES if name not in _CHANNEL_FIELDS)
+_TAIL_KEYS = {**_TAIL_FIELDS, **{name: (name,) for name in TAIL_LOSSES}}
 
 
 def _tail_layout(tail, start, width):
@@ -440,7 +474,7 @@ def pack_local(stats=None, mse=None, status=None, rmsd=None, channels=None, allo
     B = next((t.shape[0] for name, t in {**given, **tailed}.items() if name not in ("mse", "status")), 0)
     at, size = _local_layout(B, tuple(given))
     if tail:
-        tail_at, size = _tail_layout(tail, size, lambda field, t: 0 if t is None else len(_TAIL_FIELDS[field]) * B)
+        tail_at, size = _tail_layout(tail, size, lambda field, t: 0 if t is None else len(_TAIL_KEYS[field]) * B)
         at, given = {**at, **tail_at}, {**given, **tailed}
     buf = alloc(size)
     for name, t in given.items():
@@ -467,7 +501,7 @@ def unpack_local(host, layout, n_res=None):
         if field in at:
             values = host[at[field]].reshape(B, len(keys))
             out.update({key: finite_mean(values[:, k]) for k, key in enumerate(keys)})
-    for field, keys in _TAIL_FIELDS.items():
+    for field, keys in _TAIL_KEYS.items():
         if field in at:                               # asked for: the keys exist, None when no value was passed
             values = host[at[field]].reshape(-1, len(keys))
             out.update({key: finite_mean(values[:, k]) if len(values) else None for k, key in enumerate(keys)})
@@ -484,7 +518,7 @@ VECTOR_SLOTS, VECTOR_SIZE = _take([("sums", 4), ("proteins", 1), ("rmsd_sum", 1)
 def _vector_tail(tail):
     """({field asked for: its slice behind VECTOR_SLOTS}, the vector's size): a field's `finite_sums`, whether or not the rank has a
     value - the length depends on what was ASKED alone, so an empty shard adds a vector as long as the others'."""
-    return _tail_layout(tail, VECTOR_SIZE, lambda field, t: 2 * len(_TAIL_FIELDS[field]))
+    return _tail_layout(tail, VECTOR_SIZE, lambda field, t: 2 * len(_TAIL_KEYS[field]))
 
 
 def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, channels=None, device=None, tail=None):
@@ -529,7 +563,7 @@ def unpack_global(v, passed=(), tail=()):
     for field, at in _vector_tail(dict.fromkeys(tail))[0].items():
         total, count = v[at].reshape(2, -1)
         out.update({key: total[k] / count[k] if count[k] > 0 else float("nan") if field in passed else None
-                    for k, key in enumerate(_TAIL_FIELDS[field])})
+                    for k, key in enumerate(_TAIL_KEYS[field])})
     return out
 
 
@@ -549,18 +583,21 @@ class LossReport:
     """
 
     def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, clash=None, with_clash=False,
-                 tm=None, with_tm=False, lddt=None, slddt=None, fape=None):
+                 tm=None, with_tm=False, kabsch=None, with_kabsch=False, lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
         `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None.
         `clash`: the per-protein clash losses [B] (`--clash_weight`, `--eval_clash`) or None; `with_clash`: the job reports them -
         true on EVERY rank then, also on one whose shard is empty and has none: the report carries the tail for them, and `wait()`
         the key `clash`.
         `tm`: the per-protein scores [B,3] of eval_metrics.tm_batch (evaluation under --eval_tm) or None; `with_tm` as `with_clash`:
-        one more tail field of three columns, and `wait()` the keys `tm-ca`, `gdt-ts`, `gdt-ha`."""
+        one more tail field of three columns, and `wait()` the keys `tm-ca`, `gdt-ts`, `gdt-ha`.
+        `kabsch`: the per-protein losses [B] of batch_loss under `-l kabsch` or None; `with_kabsch` as `with_clash` (true on every
+        rank of such a run): the last tail field, and `wait()` the key `kabsch`, reduced like `slddt` and `fape`."""
         self.world, self.n_res = dp.world_size(), n_res
         channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
         tail = {**({"clash": clash} if with_clash or clash is not None else {}),
-                **({"tm": tm} if with_tm or tm is not None else {})} or None
+                **({"tm": tm} if with_tm or tm is not None else {}),
+                **({"kabsch": kabsch} if with_kabsch or kabsch is not None else {})} or None
         if self.world == 1:
             buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
                                      alloc=lambda n: _pinned("report32", n, torch.float32, device), tail=tail)

@@ -30,8 +30,8 @@ from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_l
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
 from .losses import (CLASH_BACKBONE_MESSAGE, CLASH_NO_STRUCTURE_MESSAGE, CLASH_TOLERANCE, EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE,
-                     RENAME_NO_STRUCTURE_MESSAGE, BatchLoss, LossReport, batch_loss, clash_check, combine_drmsd_mse, mse_grad,
-                     mse_sums, predicted_coords)
+                     RENAME_NO_STRUCTURE_MESSAGE, TAIL_LOSSES, BatchLoss, LossReport, batch_loss, clash_check, combine_drmsd_mse,
+                     mse_grad, mse_sums, predicted_coords)
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
 from .optim import FusedAdam, FusedSGD, ScheduledOptim
@@ -121,12 +121,15 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     lDDT (eval_metrics.lddt_batch, on the coordinates built for the dRMSD and `rmsd-full`) over the proteins of the global batch
     that have a score.  Without the flag, and in every training step, nothing is computed and the keys are absent.
 
-    `-l slddt`, `-l fape` (losses.EXTRA_LOSSES; not in the reference): the structure is trained on that loss.  The injected
+    `-l slddt`, `-l fape`, `-l kabsch` (losses.EXTRA_LOSSES; not in the reference): the structure is trained on that loss.  The injected
     gradient is d(sum_i loss_i), the SUM over proteins; `loss` and the new key `<name>-full` are the mean of the per-protein losses
     over the proteins of the GLOBAL batch that have a finite one.  The ten reference keys keep their meaning: the dRMSD statistics
     are taken forward-only on the coordinates already built, as is the loss itself in `eval_mode`.  Under any other `-l` no key.
       slddt: the smooth lDDT loss of csrc/slddt.hip (`--slddt_cutoff`, `--slddt_temperature`; definition in include/ptamd.h).
-      fape: the frame aligned point error of csrc/fape.hip (`--fape_clamp`): it alone tells a structure from its mirror image.
+      fape: the frame aligned point error of csrc/fape.hip (`--fape_clamp`); it tells a structure from its mirror image.
+      kabsch: the all-atom RMSD after optimal superposition over proper rotations, of csrc/kabsch_loss.hip (no parameters): the
+        metric `rmsd-full` as a loss - in `eval_mode` `kabsch-full` and `rmsd-full` are the same quantity from two kernels - and the
+        other loss that tells a structure from its mirror image.  Proteins with fewer than 3 present atoms have none (NaN).
 
     `args.rename_symmetric` (losses.rename_symmetric; not in the reference): the structure is built first and the truth - coordinates
     and angles - renamed against it at its symmetric side chains (ASP, GLU, PHE, TYR); every number above, every gradient, the MSE,
@@ -193,6 +196,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             tm = tm_batch(res.crd, tgt_crds, src_seq)[0]
     report = LossReport(dev, stats=res.stats, status=res.status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
                         **({extra.name: res.per_protein} if extra is not None else {}),
+                        **({f"with_{extra.name}": True} if extra is not None and extra.name in TAIL_LOSSES else {}),
                         **({"clash": clash, "with_clash": True} if want_clash else {}),
                         **({"tm": tm, "with_tm": True} if want_tm else {}))
     if do_backwards and not empty:
@@ -523,7 +527,8 @@ def determine_largest_batch_size(args, data, device, angle_means, fraction_to_ke
     return max_batch_size
 
 
-SLDDT_BACKBONE_MESSAGE, FAPE_BACKBONE_MESSAGE = (EXTRA_LOSSES[name].backbone_message for name in ("slddt", "fape"))
+SLDDT_BACKBONE_MESSAGE, FAPE_BACKBONE_MESSAGE, KABSCH_BACKBONE_MESSAGE = (EXTRA_LOSSES[name].backbone_message
+                                                                          for name in ("slddt", "fape", "kabsch"))
 
 
 class _Parser(argparse.ArgumentParser):
@@ -546,7 +551,7 @@ class _Parser(argparse.ArgumentParser):
 
 def early_stopping_target(args):
     """(es_mode, es_metric) of train.py:567: `-esm <train|test|valid-NN>-<loss name>`, by default the training loss of the run.
-    (Loss names carry no hyphen - `slddt`, `fape` - because of this split.)"""
+    (Loss names carry no hyphen - `slddt`, `fape`, `kabsch` - because of this split.)"""
     return tuple((args.early_stopping_metric or f"train-{args.loss}").rsplit("-", 1))
 
 
@@ -569,7 +574,8 @@ def create_parser():
     training.add_argument('-cg', '--clip', type=float, default=1)
     training.add_argument('-l', '--loss', choices=["mse", "drmsd", "lndrmsd", "combined", *EXTRA_LOSSES], default="combined",
                           help="slddt (not in the reference): the smooth lDDT loss of AlphaFold 3 over all atoms; fape (not in "
-                               "the reference): the frame aligned point error of AlphaFold 2, backbone frames x all atoms")
+                               "the reference): the frame aligned point error of AlphaFold 2, backbone frames x all atoms; kabsch (not "
+                               "in the reference): the all-atom RMSD after optimal superposition, the metric rmsd-full as a loss")
     training.add_argument('--train_only', action='store_true')
     training.add_argument('--lr_scheduling', type=str, choices=['noam', 'plateau'], default='plateau')
     training.add_argument('--patience', type=int, default=10)
