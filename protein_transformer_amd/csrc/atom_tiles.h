@@ -1,6 +1,8 @@
 // The compacted atom tiles that the lDDT family sweeps: csrc/lddt.hip (the metric) and csrc/slddt.hip (the training loss) read
 // the same records, so which atoms exist - the pad test, the NaN test and slot order - is decided here and nowhere else.
-// csrc/fape.hip (the FAPE training loss) sweeps the same atoms against backbone frames.
+// csrc/fape.hip (the FAPE training loss) sweeps the same atoms against backbone frames.  csrc/pair_sweep.h builds the sweep that
+// csrc/slddt.hip and csrc/clash.hip share on these tiles; csrc/clash.hip fills them with a compaction of its own (presence by
+// residue type, boxes of the prediction) from the pieces below.
 // csrc/drmsd.hip packs differently on purpose (backbone first, an interleaved record) and is not a user of this header.
 #pragma once
 #include <limits.h>
@@ -49,13 +51,33 @@ struct TileLayout {
 // aux = slot.  Unusable = not finite, or beyond 1e18 (squared differences would not be finite): replaced by 0 and marked, so
 // nothing non-finite enters a sweep.
 constexpr float PRED_MAX = 1.0e18f;
+__device__ __forceinline__ bool pred_unusable(float px, float py, float pz) {
+  return !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
+}
 struct SlotRecord {
   static __device__ __forceinline__ Atom8 make(float px, float py, float pz, float tx, float ty, float tz, int res, int slot) {
-    const bool bad = !(fabsf(px) <= PRED_MAX && fabsf(py) <= PRED_MAX && fabsf(pz) <= PRED_MAX);   // (NaN fails every test)
+    const bool bad = pred_unusable(px, py, pz);
     if (bad) px = py = pz = 0.f;
     return Atom8{px, py, pz, tx, ty, tz, (res << 1) | (int)bad, slot};
   }
 };
+
+// the bounding boxes of the tiles of a protein's n compacted atoms, by the wavefronts of the workgroup that wrote the atoms, behind
+// its barrier.  get(j, x, y, z) reads the boxed coordinate of atom j
+template <class Get>
+__device__ __forceinline__ void tile_boxes(int n, Box8 *boxes, Get get) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float inf = __builtin_inff();
+  for (int t = w; t * TS < n; t += COMPACT_THREADS / 64) {
+    const int j = t * TS + lane;
+    const bool live = j < n;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (live) get(j, x, y, z);
+    const float lox = wave_min(live ? x : inf), loy = wave_min(live ? y : inf), loz = wave_min(live ? z : inf);
+    const float hix = wave_max(live ? x : -inf), hiy = wave_max(live ? y : -inf), hiz = wave_max(live ? z : -inf);
+    if (lane == 0) boxes[t] = Box8{lox, loy, loz, hix, hiy, hiz, 0.f, 0.f};
+  }
+}
 
 // ---- compaction.  One workgroup per protein; each of its 16 wavefronts owns a contiguous share of the atom slots and walks it
 // 64 slots at a time (position of a present atom = atoms in the shares before + running count + rank among the lanes before
@@ -109,19 +131,10 @@ __global__ __launch_bounds__(COMPACT_THREADS) void compact_kernel(const float *_
   }
   if (tid == 0) natoms[b] = n;
   __syncthreads();   // the atoms this workgroup wrote are visible to all of it
-  const float inf = __builtin_inff();
-  for (int t = w; t * TS < n; t += NWAVE) {
-    const int j = t * TS + lane;
-    const bool live = j < n;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (live) {
-      const Atom8 a = atoms[j];
-      x = a.tx; y = a.ty; z = a.tz;
-    }
-    const float lox = wave_min(live ? x : inf), loy = wave_min(live ? y : inf), loz = wave_min(live ? z : inf);
-    const float hix = wave_max(live ? x : -inf), hiy = wave_max(live ? y : -inf), hiz = wave_max(live ? z : -inf);
-    if (lane == 0) boxes[t] = Box8{lox, loy, loz, hix, hiy, hiz, 0.f, 0.f};
-  }
+  tile_boxes(n, boxes, [&](int j, float &x, float &y, float &z) __attribute__((always_inline)) {
+    const Atom8 a = atoms[j];
+    x = a.tx; y = a.ty; z = a.tz;
+  });
 }
 
 // can a pair of atoms of two tiles be included?  Its true distance is at least the gap between the boxes; 0.1 % on the squares
