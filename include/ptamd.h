@@ -230,6 +230,49 @@ size_t ptamd_tm_workspace_bytes(int B, int L);
 int ptamd_tm_score(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *score, int32_t *counts,
                    float *xform, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Secondary-structure agreement, for a whole batch (csrc/dssp.hip): the metrics `ss-q3`, `ss-h`, `ss-e` of `train.py --eval_ss`.
+ * The reference has no counterpart.  Both structures get a three-state string by the method of Kabsch & Sander, "Dictionary of
+ * protein secondary structure: pattern recognition of hydrogen-bonded and geometrical features", Biopolymers 22:2577-2637 (1983)
+ * - backbone hydrogen bonds from an electrostatic energy, turns, helices and bridges from the bond pattern - and the agreement
+ * of the strings is Q3.  This is DSSP SIMPLIFIED: every bond under the energy threshold counts, where the DSSP program keeps
+ * only the two strongest bonds per group; bends and turns are not states; isolated bridges (B) and ladders (E) are not told
+ * apart; three states, not eight.  PARITY UNPINNED: what is pinned is this definition, restated in numpy fp64 by tests/ss_ref.py.
+ * Inputs as for ptamd_lddt; the backbone slots of a residue are 0 N, 1 CA, 2 C, 3 O.
+ *   Presence.  Residue r is PRESENT when seq[r] is not PTAMD_PAD_ID and none of its four TRUE backbone atoms has a NaN
+ *   coordinate.  The same mask is applied to the prediction: a residue absent from the truth is absent from both structures, so
+ *   both see the same chain breaks.  What the prediction holds never decides presence.  A non-finite predicted coordinate on a
+ *   backbone atom of a present residue - the rule of ptamd_kabsch_rmsd - makes the three scores of that protein NaN, its
+ *   confusion counts 0, its predicted states -1 and the bond bits of its prediction unspecified; its true states and bits, and
+ *   every other protein, are what they would be.
+ *   Amide hydrogen.  Residue j has an H when j-1 and j are present: H_j = N_j + (C_{j-1} - O_{j-1}) / |C_{j-1} - O_{j-1}|.
+ *   H-bond hb(i,j), the C=O of i accepting from the N-H of j: i and j present, j has an H, |i - j| >= 2, and
+ *   E = 27.888 (1/r(O_i,N_j) + 1/r(C_i,H_j) - 1/r(O_i,H_j) - 1/r(C_i,N_j)) kcal/mol < -0.5, strictly; a distance below 0.5 A is
+ *   taken as 0.5 A.  EVERY bond under the threshold counts (the simplification above).
+ *   Turns and helices.  n-turn at i, n = 3, 4, 5: hb(i, i+n) with i .. i+n all present.  Two consecutive n-turns at i-1 and i
+ *   put the residues i .. i+n-1 in an n-helix.
+ *   Bridges.  Partners i, j need |i - j| >= 3 with i-1 .. i+1 and j-1 .. j+1 all present.  Parallel: [hb(i-1,j) and hb(j,i+1)]
+ *   or [hb(j-1,i) and hb(i,j+1)].  Antiparallel: [hb(i,j) and hb(j,i)] or [hb(i-1,j+1) and hb(j-1,i+1)].  A residue with any
+ *   bridge partner is a strand residue.
+ *   State of a present residue: H (0) in a 4-helix; else E (1) if a strand residue; else H in a 3-helix or a 5-helix; else
+ *   C (2).  Absent and pad residues: -1.
+ *   Scores per protein over its n present residues: q3 = the share with pred state == true state; h = the share of the true-H
+ *   residues predicted H; e = the share of the true-E residues predicted E; each NaN when its denominator is 0.
+ *   score [B,3] out = {q3, h, e}; confusion [B,3,3] out: confusion[t][p] = present residues of true state t and predicted
+ *   state p (states in the order H, E, C); states [B,L,2] out or NULL = {pred, true} per residue; hbonds [B,2,L,ceil(L/64)] out
+ *   or NULL: structure 0 the prediction, 1 the truth; bit (j & 63) of word j >> 6 of row i = hb(i,j).
+ * Energies are fp32 on the fp32 inputs (H is rounded to fp32 once; v_rsq_f32 on the squared distances): a pair whose fp64 energy
+ * lies within 2e-3 kcal/mol of -0.5 may be decided either way for coordinates within +-64 A (tests/ss_ref.py derives the
+ * figure); outside that band the bits, and everything derived from them, are exact.  All results are integers or ratios of
+ * integers rounded once; no atomics; two runs give the same bits, and a protein's result does not depend on the batch around
+ * it or on how far its row is padded.  Workspace: 128 B per residue slot for the backbone records of both structures and
+ * L^2 / 4 bytes per protein for the bond bits of both, used when hbonds is NULL - a function of (B, L) only; B = 32, L = 512:
+ * 4.2e6 bytes.  A NULL pred_crd, true_crd, seq, score or confusion, B or L <= 0, or L beyond INT_MAX / 28 (the bound of
+ * ptamd_lddt): PTAMD_ERR_BAD_SHAPE; workspace NULL or too small: PTAMD_ERR_WORKSPACE; nothing is launched or written then.  No
+ * state between calls, nothing read from the environment. */
+size_t ptamd_ss_workspace_bytes(int B, int L);
+int ptamd_ss(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *score, int32_t *confusion,
+             int8_t *states, uint64_t *hbonds, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
  * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
  * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the

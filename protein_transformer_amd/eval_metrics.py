@@ -17,6 +17,10 @@ The steric clash term (`clash_batch`; `train.py --eval_clash`) has none either: 
 TM-score and GDT_TS / GDT_HA (`tm_batch`, `batch_tm`; `train.py --eval_tm`) have none either: Zhang & Skolnick, Proteins
 57:702-710 (2004), over the C-alphas, maximised by the seed-and-refine superposition search of the TMscore program on the device
 (csrc/tmscore.hip; definition in include/ptamd.h; PARITY UNPINNED like the Kabsch RMSD above).
+
+Secondary-structure agreement (`ss_batch`; `train.py --eval_ss`) has none either: Kabsch & Sander, Biopolymers 22:2577-2637
+(1983), simplified - every hydrogen bond under the energy threshold counts, three states H / E / C - for both structures, and Q3
+between them (csrc/dssp.hip; definition in include/ptamd.h; PARITY UNPINNED).
 """
 import numpy as np
 import torch
@@ -74,6 +78,28 @@ def tm_batch(pred_crd, true_crd, seq):
                                    _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "tm_score")
     return score, counts, torch.cat([xform[:, :9].reshape(B, 3, 3), xform[:, 9:].reshape(B, 3, 1)], dim=2)
+
+
+def ss_batch(crd, true_crds, seq, hbonds=False):
+    """crd, true_crds [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] -> (score [B,3] = {q3, h, e},
+    confusion [B,3,3] int32 = true state x predicted state in the order H, E, C, states [B,L,2] int8 = {pred, true}, -1 = absent),
+    all on the device, no sync: the simplified DSSP of csrc/dssp.hip on both structures (definition in include/ptamd.h).  NaN = no
+    residue in the denominator, or a non-finite predicted backbone atom on a present residue.  `hbonds`: also the bond bits
+    [B, 2, L, ceil(L/64)] int64 ({pred, true}; bit j & 63 of word j >> 6 of row i = the C=O of i accepts from the N-H of j)."""
+    _lib.require_gpu(crd, true_crds, seq)
+    B, L = seq.shape
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    dev = seq.device
+    score = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    confusion = torch.empty(B, 3, 3, dtype=torch.int32, device=dev)
+    states = torch.empty(B, L, 2, dtype=torch.int8, device=dev)
+    bits = torch.empty(B, 2, L, (L + 63) // 64, dtype=torch.int64, device=dev) if hbonds else None
+    ws = _lib.workspace("ss", _lib.lib().ptamd_ss_workspace_bytes(B, L), dev)
+    rc = _lib.lib().ptamd_ss(_lib.ptr(crd.float().contiguous()), _lib.ptr(true_crds.float().contiguous()),
+                             _lib.ptr(seq.contiguous()), B, L, _lib.ptr(score), _lib.ptr(confusion), _lib.ptr(states),
+                             _lib.ptr(bits), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "ss")
+    return (score, confusion, states, bits) if hbonds else (score, confusion, states)
 
 
 def clash_batch(crd, seq, tolerance=1.5):

@@ -28,6 +28,10 @@ _CLASH = ("clash-full",)
 # `train.py --eval_tm` (evaluation only): TM-score and GDT_TS / GDT_HA over the C-alphas, kept like the lDDT pair
 _TM = ("tm-ca", "gdt-ts", "gdt-ha")
 _OPTIONAL = _LDDT + _CLASH + _TM
+# `train.py --eval_ss` (evaluation only): secondary-structure agreement - Q3 and the recall of the true helix and strand residues -
+# kept like the lDDT pair, behind everything above; HIGHER is better, also as `-esm <split>-ss-q3` (es_sign below)
+_SS = ("ss-q3", "ss-h", "ss-e")
+_KEPT = _OPTIONAL + _SS
 # `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
 # above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
 # exactly their keys
@@ -68,7 +72,7 @@ def reset_metrics_for_epoch(metrics, mode):
     m = metrics.setdefault(mode, _split_metrics(_extra(metrics.get("train", {}))))
     for k in _TRACKED + tuple(f"{x}-full" for x in _extra(m)):
         m[f"epoch-{k}"] = m[f"batch-{k}"] = 0
-    for k in _OPTIONAL:
+    for k in _KEPT:
         for prefix in ("epoch", "batch", "sum", "n"):
             m.pop(f"{prefix}-{k}", None)
     m["batch-history"], m["speed-history"] = [], []
@@ -94,7 +98,7 @@ def update_metrics(metrics, losses, mode, src_seq, tracking_loss=None, batch_lev
         if batch_level:
             m[f"batch-{x}-full"] = v
         m[f"epoch-{x}-full"] += v
-    for k in _OPTIONAL:
+    for k in _KEPT:
         if k in losses:                               # a batch without any scored protein reports NaN and is left out
             v = _num(losses[k])
             if batch_level:                           # (training steps under --clash_weight: their rows carry the step's value)
@@ -122,9 +126,12 @@ def update_metrics_end_of_epoch(metrics, mode):
     for k in ("drmsd-full", "lndrmsd-full", "mse-full", "drmsd-bb", "lndrmsd-bb", "mse-bb", "mse-sc", "rmsd-full"):
         m[f"epoch-{k}"] /= n
     m["epoch-combined-full"] = 0 if m["epoch-drmsd-full"] == 0 else m["epoch-combined-full"] / n
-    for k in _OPTIONAL:
+    for k in _KEPT:
         if f"n-{k}" in m:
             m[f"epoch-{k}"] = m[f"sum-{k}"] / m[f"n-{k}"] if m[f"n-{k}"] else float("nan")
+    for k in _SS:
+        if f"n-{k}" in m:                               # (a history only where the metric is reported: `-esm` reads it)
+            m.setdefault(f"epoch-history-{k}", []).append(m[f"epoch-{k}"])
     for h in _HISTORY:
         m[f"epoch-history-{h}"].append(m[f"epoch-{h}-full"])
     for x in _extra(m):
@@ -133,9 +140,18 @@ def update_metrics_end_of_epoch(metrics, mode):
     return metrics
 
 
+def es_value(args, metrics):
+    """What early stopping, the plateau scheduler and the checkpoint policy compare, LOWER being better: `epoch-<es_metric>-full`
+    of the split `es_mode` - or, for a secondary-structure score (`-esm <split>-ss-q3`, `--eval_ss`), where higher is better, its
+    negative.  Returns (value, history)."""
+    m = metrics[args.es_mode]
+    if args.es_metric in _SS:
+        return -m.get(f"epoch-{args.es_metric}", float("nan")), [-v for v in m.get(f"epoch-history-{args.es_metric}", [])]
+    return m[f"epoch-{args.es_metric}-full"], m[f"epoch-history-{args.es_metric}"]
+
+
 def update_loss_trackers(args, epoch_i, metrics):
-    loss_to_compare = metrics[args.es_mode][f"epoch-{args.es_metric}-full"]
-    losses_to_compare = metrics[args.es_mode][f"epoch-history-{args.es_metric}"]
+    loss_to_compare, losses_to_compare = es_value(args, metrics)
     if metrics["best_valid_loss_so_far"] - loss_to_compare > args.early_stopping_threshold:
         metrics["best_valid_loss_so_far"] = loss_to_compare
         metrics["epoch_last_improved"] = epoch_i
@@ -154,12 +170,14 @@ def prepare_log_header(args):
     tail = ',lddt,lddt_ca' if getattr(args, "eval_lddt", False) else ''      # two trailing columns under --eval_lddt only
     tail += ',clash' if getattr(args, "eval_clash", False) else ''            # one more, behind them, under --eval_clash only
     tail += ',tm,gdt_ts,gdt_ha' if getattr(args, "eval_tm", False) else ''    # three more, behind those, under --eval_tm only
+    tail += ',ss_q3,ss_h,ss_e' if getattr(args, "eval_ss", False) else ''     # three more, behind those, under --eval_ss only
     if args.loss == "combined":
         return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed' + tail
     return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed' + tail
 
 
-def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False, tm=False):
+def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False, tm=False,
+              ss=False):
     """One CSV row (log.py:115-130): ten values - drmsd, ln_drmsd, rmse, rmsd, combined, lr, mode, granularity, time,
     speed; like upstream the `combined` value is written whatever the header of `prepare_log_header` lists.  One
     deliberate difference: the granularity column says "batch" for per-batch rows (upstream writes the literal "epoch"
@@ -167,7 +185,8 @@ def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False,
     upstream column byte for byte for consumers of the reference's `.train` files.  `lddt` (`train.py --eval_lddt`): two
     trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it).  `clash`
     (`train.py --eval_clash`): one more trailing value, the epoch's clash-full, nan on rows that have none.  `tm`
-    (`train.py --eval_tm`): three more, the epoch's tm-ca, gdt-ts and gdt-ha, nan on rows that have none."""
+    (`train.py --eval_tm`): three more, the epoch's tm-ca, gdt-ts and gdt-ha, nan on rows that have none.  `ss`
+    (`train.py --eval_ss`): three more, the epoch's ss-q3, ss-h and ss-e, nan on rows that have none."""
     t = t or time.time()
     m = metrics[mode]
     be = "epoch" if end_of_epoch else "batch"
@@ -182,6 +201,8 @@ def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False,
         row += [m.get(f"{be}-{k}", float("nan")) for k in _CLASH]
     if tm:
         row += [m.get(f"{be}-{k}", float("nan")) for k in _TM]
+    if ss:
+        row += [m.get(f"{be}-{k}", float("nan")) for k in _SS]
     log_writer.writerow(row)
 
 
@@ -194,7 +215,8 @@ def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer
     metrics["history-lr"].append(lr)
     if dp.is_main():
         log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)),
-                  clash=bool(getattr(args, "eval_clash", False)), tm=bool(getattr(args, "eval_tm", False)))
+                  clash=bool(getattr(args, "eval_clash", False)), tm=bool(getattr(args, "eval_tm", False)),
+                  ss=bool(getattr(args, "eval_ss", False)))
         if step % max(1, getattr(args, "log_wandb_step", 1) * 10) == 0:
             m = metrics["train"]
             print(f"  step {step:5d}  drmsd {m['batch-drmsd-full']:.4f}  ln {m['batch-lndrmsd-full']:.6f}  "
@@ -238,6 +260,6 @@ def do_eval_epoch_logging(metrics, mode):
     update_metrics_end_of_epoch(metrics, mode)
     if dp.is_main():
         m = metrics[mode]
-        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _OPTIONAL if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash, --eval_tm only
+        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _KEPT if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash, --eval_tm, --eval_ss only
         print(f"  [{mode}] drmsd {m['epoch-drmsd-full']:.4f}  ln {m['epoch-lndrmsd-full']:.6f}  "
               f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}{tail}", flush=True)

@@ -455,7 +455,10 @@ _TAIL_FIELDS = {"clash": ("clash",), "tm": ("tm-ca", "gdt-ts", "gdt-ha")}
 # ... and behind those the extra losses that have no channel in the fixed part (`kabsch`): one column each, asked for in the runs
 # whose loss it is (LossReport's keyword with_<name>)
 TAIL_LOSSES = tuple(name for name in EXTRA_LOSSES if name not in _CHANNEL_FIELDS)
-_TAIL_KEYS = {**_TAIL_FIELDS, **{name: (name,) for name in TAIL_LOSSES}}
+# ... and behind those the evaluation metrics that came after them, in a registry of their own so that the two above stay what they
+# are: `ss` (--eval_ss), three columns
+_TAIL_METRICS = {"ss": ("ss-q3", "ss-h", "ss-e")}
+_TAIL_KEYS = {**_TAIL_FIELDS, **{name: (name,) for name in TAIL_LOSSES}, **_TAIL_METRICS}
 
 
 def _tail_layout(tail, start, width):
@@ -583,7 +586,7 @@ class LossReport:
     """
 
     def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, clash=None, with_clash=False,
-                 tm=None, with_tm=False, kabsch=None, with_kabsch=False, lddt=None, slddt=None, fape=None):
+                 tm=None, with_tm=False, kabsch=None, with_kabsch=False, ss=None, with_ss=False, lddt=None, slddt=None, fape=None):
         """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
         `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None.
         `clash`: the per-protein clash losses [B] (`--clash_weight`, `--eval_clash`) or None; `with_clash`: the job reports them -
@@ -592,12 +595,15 @@ class LossReport:
         `tm`: the per-protein scores [B,3] of eval_metrics.tm_batch (evaluation under --eval_tm) or None; `with_tm` as `with_clash`:
         one more tail field of three columns, and `wait()` the keys `tm-ca`, `gdt-ts`, `gdt-ha`.
         `kabsch`: the per-protein losses [B] of batch_loss under `-l kabsch` or None; `with_kabsch` as `with_clash` (true on every
-        rank of such a run): the last tail field, and `wait()` the key `kabsch`, reduced like `slddt` and `fape`."""
+        rank of such a run): one more tail field, and `wait()` the key `kabsch`, reduced like `slddt` and `fape`.
+        `ss`: the per-protein scores [B,3] of eval_metrics.ss_batch (evaluation under --eval_ss) or None; `with_ss` as `with_clash`:
+        the last tail field, three columns, and `wait()` the keys `ss-q3`, `ss-h`, `ss-e`."""
         self.world, self.n_res = dp.world_size(), n_res
         channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
         tail = {**({"clash": clash} if with_clash or clash is not None else {}),
                 **({"tm": tm} if with_tm or tm is not None else {}),
-                **({"kabsch": kabsch} if with_kabsch or kabsch is not None else {})} or None
+                **({"kabsch": kabsch} if with_kabsch or kabsch is not None else {}),
+                **({"ss": ss} if with_ss or ss is not None else {})} or None
         if self.world == 1:
             buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
                                      alloc=lambda n: _pinned("report32", n, torch.float32, device), tail=tail)

@@ -25,8 +25,9 @@ import torch
 
 from . import dp
 from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
-from .eval_metrics import clash_batch, kabsch_rmsd_batch, lddt_batch, tm_batch
-from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging,
+from .eval_metrics import clash_batch, kabsch_rmsd_batch, lddt_batch, ss_batch, tm_batch
+from .log import _SS as SS_KEYS
+from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging, es_value,
                   init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
 from .losses import (CLASH_BACKBONE_MESSAGE, CLASH_NO_STRUCTURE_MESSAGE, CLASH_TOLERANCE, EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE,
@@ -38,6 +39,7 @@ from .optim import FusedAdam, FusedSGD, ScheduledOptim
 from .protein.Sequence import VOCAB
 from .protein.Structure import NUM_PREDICTED_ANGLES, raise_for_status
 
+SS_ESM_MESSAGE = "-esm <split>-ss-q3 / -ss-h / -ss-e needs --eval_ss: nothing computes the score without it"
 START_EPOCH = 0
 START_TIME = time.time()
 
@@ -149,6 +151,12 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     GLOBAL batch that have a finite score, from the coordinates evaluation has already built (all atoms, also under
     `args.backbone_loss` and `args.rename_symmetric`).  Without the flag, and in every training step - where, under `-l mse`, no
     structure exists - nothing is computed and the keys are absent.
+
+    `args.eval_ss` (eval_metrics.ss_batch; Kabsch & Sander's DSSP, simplified, on both structures; not in the reference): in
+    `eval_mode` the dictionary gains `ss-q3`, `ss-h` and `ss-e` - the three-state agreement and the recall of the true helix and
+    strand residues - each the mean over the proteins of the GLOBAL batch that have a finite one, from the coordinates evaluation
+    has already built (also under `args.backbone_loss` and `args.rename_symmetric`: the backbone is not renamed).  Without the
+    flag, and in every training step, nothing is launched and the keys are absent.
     """
     dev = src_seq.device
     empty = src_seq.shape[0] == 0
@@ -159,6 +167,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         raise ValueError(extra.backbone_message)
     want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
     want_tm = eval_mode and bool(getattr(args, "eval_tm", False))
+    want_ss = eval_mode and bool(getattr(args, "eval_ss", False))
     rename = bool(getattr(args, "rename_symmetric", False))
     if rename and (backbone or not need_drmsd):
         raise ValueError(RENAME_BACKBONE_MESSAGE if backbone else RENAME_NO_STRUCTURE_MESSAGE)
@@ -169,7 +178,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     structure = need_drmsd and not empty
     compact = backbone and not eval_mode       # a training step under --backbone_loss builds no side chains: N, CA, C alone
     res = BatchLoss()
-    grad = sums = rmsd = lddt = clash = tm = None
+    grad = sums = rmsd = lddt = clash = tm = ss = None
     if structure:
         # the structure (and the renaming) come first: the MSE, the RMSD and the lDDT below see the truth the losses saw
         kw = dict(do_backward=do_backwards and (compact or not backbone), backbone_only=compact, rename_symmetric=rename,
@@ -194,11 +203,14 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
             clash = clash_batch(res.crd, src_seq, clash_tol)[0]
         if want_tm:                            # (--rename_symmetric renames side-chain atoms: the C-alphas are the same)
             tm = tm_batch(res.crd, tgt_crds, src_seq)[0]
+        if want_ss:                            # (nor does the renaming touch N, CA, C, O)
+            ss = ss_batch(res.crd, tgt_crds, src_seq)[0]
     report = LossReport(dev, stats=res.stats, status=res.status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
                         **({extra.name: res.per_protein} if extra is not None else {}),
                         **({f"with_{extra.name}": True} if extra is not None and extra.name in TAIL_LOSSES else {}),
                         **({"clash": clash, "with_clash": True} if want_clash else {}),
-                        **({"tm": tm, "with_tm": True} if want_tm else {}))
+                        **({"tm": tm, "with_tm": True} if want_tm else {}),
+                        **({"ss": ss, "with_ss": True} if want_ss else {}))
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -247,6 +259,8 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         out["lddt-full"], out["lddt-ca"] = channel("lddt"), channel("lddt-ca")
     if want_tm:         # --eval_tm: three more keys, means over the proteins of the GLOBAL batch that have a score
         out["tm-ca"], out["gdt-ts"], out["gdt-ha"] = channel("tm-ca"), channel("gdt-ts"), channel("gdt-ha")
+    if want_ss:         # --eval_ss: three more keys, means over the proteins of the GLOBAL batch that have a score
+        out["ss-q3"], out["ss-h"], out["ss-e"] = channel("ss-q3"), channel("ss-h"), channel("ss-e")
     if host["n_res"] is not None:
         out["n-residues"] = host["n_res"]                      # residues of the GLOBAL batch (speed meter, log.py)
     return out
@@ -269,7 +283,7 @@ def eval_epoch(model, validation_data, device, args, metrics, mode="valid", pool
 def train(model, metrics, training_data, train_eval_loader, validation_datasets, test_data, optimizer, device, args,
           log_writer, scheduler, drmsd_worker_pool):
     """ Model training control loop (train.py:138-186). """
-    columns = {k: getattr(args, f"eval_{k}", False) for k in ("lddt", "clash", "tm")}      # log_batch: the rows' trailing columns
+    columns = {k: getattr(args, f"eval_{k}", False) for k in ("lddt", "clash", "tm", "ss")}      # log_batch: the rows' trailing columns
     for epoch_i in range(START_EPOCH, args.epochs):
         if dp.is_main():
             print(f'[ Epoch {epoch_i} ]')
@@ -289,7 +303,7 @@ def train(model, metrics, training_data, train_eval_loader, validation_datasets,
         # every rank holds the same (globally reduced) metrics, so the scheduler, the early-stopping test and the
         # checkpoint policy below take the same branch on every rank
         if scheduler:
-            scheduler.step(metrics[args.es_mode][f"epoch-{args.es_metric}-full"])
+            scheduler.step(es_value(args, metrics)[0])
         try:
             metrics = update_loss_trackers(args, epoch_i, metrics)
         except EarlyStoppingCondition:
@@ -544,6 +558,8 @@ class _Parser(argparse.ArgumentParser):
             problem = clash_check(a.clash_weight, a.clash_tolerance)
         if not problem and a.clash_weight > 0:
             problem = CLASH_BACKBONE_MESSAGE if a.backbone_loss else CLASH_NO_STRUCTURE_MESSAGE if a.loss == "mse" else None
+        if not problem and early_stopping_target(a)[1] in SS_KEYS and not a.eval_ss:
+            problem = SS_ESM_MESSAGE
         if problem:
             self.error(problem)
         return a
@@ -551,8 +567,13 @@ class _Parser(argparse.ArgumentParser):
 
 def early_stopping_target(args):
     """(es_mode, es_metric) of train.py:567: `-esm <train|test|valid-NN>-<loss name>`, by default the training loss of the run.
-    (Loss names carry no hyphen - `slddt`, `fape`, `kabsch` - because of this split.)"""
-    return tuple((args.early_stopping_metric or f"train-{args.loss}").rsplit("-", 1))
+    (Loss names carry no hyphen - `slddt`, `fape`, `kabsch` - because of this split.)  The secondary-structure scores of
+    `--eval_ss` are metrics too, as `<split>-ss-q3`, `-ss-h`, `-ss-e`: higher is better there (log.es_value)."""
+    target = args.early_stopping_metric or f"train-{args.loss}"
+    for key in SS_KEYS:
+        if target.endswith("-" + key):
+            return target[:-len(key) - 1], key
+    return tuple(target.rsplit("-", 1))
 
 
 def create_parser():
@@ -581,7 +602,8 @@ def create_parser():
     training.add_argument('--patience', type=int, default=10)
     training.add_argument('--early_stopping_threshold', type=float, default=0.001)
     training.add_argument('-esm', '--early_stopping_metric', type=str, default=None,
-                          help="<train|test|valid-NN>-<mse|drmsd|lndrmsd|combined>")
+                          help="<train|test|valid-NN>-<mse|drmsd|lndrmsd|combined>; with --eval_ss also <...>-<ss-q3|ss-h|ss-e> "
+                               "(higher is better)")
     training.add_argument('--without_angle_means', action='store_true')
     training.add_argument('--eval_train', type=my_bool, default=False)
     training.add_argument('-opt', '--optimizer', type=str, choices=['adam', 'sgd'], default='sgd')
@@ -660,6 +682,10 @@ def create_parser():
                      help="evaluation also reports TM-score and GDT_TS / GDT_HA over the C-alphas (the superposition search of the "
                           "TMscore program, on the device): three more values on the per-epoch evaluation line, three trailing "
                           "columns in the .train log")
+    new.add_argument("--eval_ss", action="store_true",
+                     help="evaluation also reports the secondary-structure agreement of prediction and truth (Kabsch & Sander's DSSP, "
+                          "simplified, on the device): Q3 and the recall of the true helix and strand residues - three more values on "
+                          "the per-epoch evaluation line, three trailing columns in the .train log; usable as -esm <split>-ss-q3")
     new.add_argument("--synthetic", type=str, default=None,
                      help="'B,L[,n_batches]': train on generated fixed-length batches instead of --data.")
     new.add_argument("--log_dir", type=str, default="../data/logs")
