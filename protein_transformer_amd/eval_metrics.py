@@ -22,21 +22,20 @@ Secondary-structure agreement (`ss_batch`; `train.py --eval_ss`) has none either
 (1983), simplified - every hydrogen bond under the energy threshold counts, three states H / E / C - for both structures, and Q3
 between them (csrc/dssp.hip; definition in include/ptamd.h; PARITY UNPINNED).
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from . import _lib
-from .protein.Structure import NUM_PREDICTED_COORDS
+from .protein.Structure import NUM_PREDICTED_COORDS, structure_pair
 
 
 def kabsch_rmsd_batch(pred_crd, true_crd, seq):
     """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] -> rmsd [B] (device, no sync)."""
-    _lib.require_gpu(pred_crd, true_crd, seq)
-    B, L = seq.shape
-    assert pred_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crd.shape == pred_crd.shape
+    pred_crd, true_crd, seq, B, L = structure_pair(pred_crd, true_crd, seq)
     out = torch.empty(B, dtype=torch.float32, device=seq.device)
-    rc = _lib.lib().ptamd_kabsch_rmsd(_lib.ptr(pred_crd.float().contiguous()), _lib.ptr(true_crd.float().contiguous()),
-                                      _lib.ptr(seq.contiguous()), B, L, _lib.ptr(out), _lib.stream())
+    rc = _lib.lib().ptamd_kabsch_rmsd(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, _lib.ptr(out), _lib.stream())
     _lib.check(rc, "kabsch_rmsd")
     return out
 
@@ -45,17 +44,14 @@ def lddt_batch(pred_crd, true_crd, seq, cutoff=15.0):
     """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] ->
     (score [B,2], per_res [B,L,2], counts [B,L,2,5] int32), all on the device, no sync.  Last-but-one axis / `score` columns:
     0 = every atom, 1 = C-alpha only; counts = {total, p0.5, p1, p2, p4} per residue (include/ptamd.h); NaN = no included pair."""
-    _lib.require_gpu(pred_crd, true_crd, seq)
-    B, L = seq.shape
-    assert pred_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crd.shape == pred_crd.shape
+    pred_crd, true_crd, seq, B, L = structure_pair(pred_crd, true_crd, seq)
     dev = seq.device
     counts = torch.empty(B, L, 2, 5, dtype=torch.int32, device=dev)       # zero-filled by the entry point
     per_res = torch.empty(B, L, 2, dtype=torch.float32, device=dev)
     score = torch.empty(B, 2, dtype=torch.float32, device=dev)
     ws = _lib.workspace("lddt", _lib.lib().ptamd_lddt_workspace_bytes(B, L), dev)
-    rc = _lib.lib().ptamd_lddt(_lib.ptr(pred_crd.float().contiguous()), _lib.ptr(true_crd.float().contiguous()),
-                               _lib.ptr(seq.contiguous()), B, L, float(cutoff), _lib.ptr(counts), _lib.ptr(per_res),
-                               _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream())
+    rc = _lib.lib().ptamd_lddt(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, float(cutoff), _lib.ptr(counts),
+                               _lib.ptr(per_res), _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "lddt")
     return score, per_res, counts
 
@@ -65,17 +61,14 @@ def tm_batch(pred_crd, true_crd, seq):
     (score [B,3] = {tm, gdt_ts, gdt_ha}, counts [B,6] int32 = {N, c0.5, c1, c2, c4, c8}, xform [B,3,4] = (R | t) with
     R p + t on q), all on the device, no sync: TM-score and GDT over the C-alphas, maximised by the seed-and-refine search of
     csrc/tmscore.hip (definition in include/ptamd.h).  NaN = fewer than 3 present C-alphas or a non-finite prediction on one."""
-    _lib.require_gpu(pred_crd, true_crd, seq)
-    B, L = seq.shape
-    assert pred_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crd.shape == pred_crd.shape
+    pred_crd, true_crd, seq, B, L = structure_pair(pred_crd, true_crd, seq)
     dev = seq.device
     score = torch.empty(B, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(B, 6, dtype=torch.int32, device=dev)
     xform = torch.empty(B, 12, dtype=torch.float32, device=dev)
     ws = _lib.workspace("tm", _lib.lib().ptamd_tm_workspace_bytes(B, L), dev)
-    rc = _lib.lib().ptamd_tm_score(_lib.ptr(pred_crd.float().contiguous()), _lib.ptr(true_crd.float().contiguous()),
-                                   _lib.ptr(seq.contiguous()), B, L, _lib.ptr(score), _lib.ptr(counts), _lib.ptr(xform),
-                                   _lib.ptr(ws), ws.numel(), _lib.stream())
+    rc = _lib.lib().ptamd_tm_score(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, _lib.ptr(score), _lib.ptr(counts),
+                                   _lib.ptr(xform), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "tm_score")
     return score, counts, torch.cat([xform[:, :9].reshape(B, 3, 3), xform[:, 9:].reshape(B, 3, 1)], dim=2)
 
@@ -86,18 +79,15 @@ def ss_batch(crd, true_crds, seq, hbonds=False):
     all on the device, no sync: the simplified DSSP of csrc/dssp.hip on both structures (definition in include/ptamd.h).  NaN = no
     residue in the denominator, or a non-finite predicted backbone atom on a present residue.  `hbonds`: also the bond bits
     [B, 2, L, ceil(L/64)] int64 ({pred, true}; bit j & 63 of word j >> 6 of row i = the C=O of i accepts from the N-H of j)."""
-    _lib.require_gpu(crd, true_crds, seq)
-    B, L = seq.shape
-    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    crd, true_crds, seq, B, L = structure_pair(crd, true_crds, seq)
     dev = seq.device
     score = torch.empty(B, 3, dtype=torch.float32, device=dev)
     confusion = torch.empty(B, 3, 3, dtype=torch.int32, device=dev)
     states = torch.empty(B, L, 2, dtype=torch.int8, device=dev)
     bits = torch.empty(B, 2, L, (L + 63) // 64, dtype=torch.int64, device=dev) if hbonds else None
     ws = _lib.workspace("ss", _lib.lib().ptamd_ss_workspace_bytes(B, L), dev)
-    rc = _lib.lib().ptamd_ss(_lib.ptr(crd.float().contiguous()), _lib.ptr(true_crds.float().contiguous()),
-                             _lib.ptr(seq.contiguous()), B, L, _lib.ptr(score), _lib.ptr(confusion), _lib.ptr(states),
-                             _lib.ptr(bits), _lib.ptr(ws), ws.numel(), _lib.stream())
+    rc = _lib.lib().ptamd_ss(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(seq), B, L, _lib.ptr(score), _lib.ptr(confusion),
+                             _lib.ptr(states), _lib.ptr(bits), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "ss")
     return (score, confusion, states, bits) if hbonds else (score, confusion, states)
 
@@ -110,6 +100,29 @@ def clash_batch(crd, seq, tolerance=1.5):
     from .losses import clash_forward_backward
     stats, nclash, _ = clash_forward_backward(crd, seq, need_grad=False, tolerance=tolerance)
     return stats[:, 0], nclash, stats[:, 1]
+
+
+def _clash_of(crd, true_crds, seq, args):
+    from .losses import CLASH_TOLERANCE
+    return clash_batch(crd, seq, float(getattr(args, "clash_tolerance", CLASH_TOLERANCE)))[0]
+
+
+# All the host code knows about an optional evaluation metric (`train.py --eval_<x>`), in the order of their columns in the log.
+# flag: the attribute of args that asks for it; field: its field in losses.REPORT_FIELDS - and the keyword of log.log_batch; columns:
+# per column of that field (key of the get_losses dictionary and of a split's metrics, name in the CSV header); run(crd, true_crds,
+# seq, args) -> the per-protein values [B] or [B,k] on the device; esm: higher is better, the keys keep an epoch-history and are
+# targets of `-esm <split>-<key>`.
+EvalMetric = namedtuple("EvalMetric", "flag field columns run esm")
+EVAL_METRICS = (
+    EvalMetric("eval_lddt", "lddt", (("lddt-full", "lddt"), ("lddt-ca", "lddt_ca")), lambda c, t, s, a: lddt_batch(c, t, s)[0], False),
+    EvalMetric("eval_clash", "clash", (("clash-full", "clash"),), _clash_of, False),
+    # (--rename_symmetric renames side-chain atoms: the C-alphas of `tm`, and N, CA, C, O of `ss`, are the same)
+    EvalMetric("eval_tm", "tm", (("tm-ca", "tm"), ("gdt-ts", "gdt_ts"), ("gdt-ha", "gdt_ha")),
+               lambda c, t, s, a: tm_batch(c, t, s)[0], False),
+    EvalMetric("eval_ss", "ss", (("ss-q3", "ss_q3"), ("ss-h", "ss_h"), ("ss-e", "ss_e")), lambda c, t, s, a: ss_batch(c, t, s)[0], True),
+)
+METRIC_KEYS = tuple(key for m in EVAL_METRICS for key, _ in m.columns)
+ESM_KEYS = tuple(key for m in EVAL_METRICS if m.esm for key, _ in m.columns)
 
 
 def rmsd(a, b):

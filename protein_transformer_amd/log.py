@@ -14,24 +14,16 @@ import numpy as np
 
 from . import dp
 from .dataset import VALID_SPLITS
+from .eval_metrics import ESM_KEYS, EVAL_METRICS, METRIC_KEYS
 from .losses import EXTRA_LOSSES
 from .protein.Sequence import VOCAB
 
 _TRACKED = ("drmsd-full", "lndrmsd-full", "mse-full", "combined-full", "rmsd-full", "drmsd-bb", "lndrmsd-bb",
             "mse-bb", "mse-sc")
 _HISTORY = ("drmsd", "combined", "lndrmsd", "mse")
-# evaluation under `train.py --eval_lddt` only (no counterpart in the reference): present in a split's metrics once a batch has
-# reported them, as sum-<k> / n-<k> over the batches with a finite value and epoch-<k> = their mean
-_LDDT = ("lddt-full", "lddt-ca")
-# `train.py --eval_clash` (evaluation) and `--clash_weight` (every step): the steric clash term, kept exactly like the lDDT pair
-_CLASH = ("clash-full",)
-# `train.py --eval_tm` (evaluation only): TM-score and GDT_TS / GDT_HA over the C-alphas, kept like the lDDT pair
-_TM = ("tm-ca", "gdt-ts", "gdt-ha")
-_OPTIONAL = _LDDT + _CLASH + _TM
-# `train.py --eval_ss` (evaluation only): secondary-structure agreement - Q3 and the recall of the true helix and strand residues -
-# kept like the lDDT pair, behind everything above; HIGHER is better, also as `-esm <split>-ss-q3` (es_sign below)
-_SS = ("ss-q3", "ss-h", "ss-e")
-_KEPT = _OPTIONAL + _SS
+# The keys of the optional metrics (eval_metrics.EVAL_METRICS: METRIC_KEYS; no counterpart in the reference) are in a split's
+# metrics once a batch has reported them, as sum-<k> / n-<k> over the batches with a finite value and epoch-<k> = their mean; those
+# of ESM_KEYS, where HIGHER is better, keep an epoch-history-<k> too and are targets of `-esm` (es_value below).
 # `train.py -l slddt` / `-l fape` only (no counterpart in the reference): the run's own loss, tracked like the `-full` losses
 # above (batch-<k>-full, epoch-<k>-full, epoch-history-<k>) in the runs whose loss it is - the metrics of every other run keep
 # exactly their keys
@@ -72,7 +64,7 @@ def reset_metrics_for_epoch(metrics, mode):
     m = metrics.setdefault(mode, _split_metrics(_extra(metrics.get("train", {}))))
     for k in _TRACKED + tuple(f"{x}-full" for x in _extra(m)):
         m[f"epoch-{k}"] = m[f"batch-{k}"] = 0
-    for k in _KEPT:
+    for k in METRIC_KEYS:
         for prefix in ("epoch", "batch", "sum", "n"):
             m.pop(f"{prefix}-{k}", None)
     m["batch-history"], m["speed-history"] = [], []
@@ -98,7 +90,7 @@ def update_metrics(metrics, losses, mode, src_seq, tracking_loss=None, batch_lev
         if batch_level:
             m[f"batch-{x}-full"] = v
         m[f"epoch-{x}-full"] += v
-    for k in _KEPT:
+    for k in METRIC_KEYS:
         if k in losses:                               # a batch without any scored protein reports NaN and is left out
             v = _num(losses[k])
             if batch_level:                           # (training steps under --clash_weight: their rows carry the step's value)
@@ -126,12 +118,11 @@ def update_metrics_end_of_epoch(metrics, mode):
     for k in ("drmsd-full", "lndrmsd-full", "mse-full", "drmsd-bb", "lndrmsd-bb", "mse-bb", "mse-sc", "rmsd-full"):
         m[f"epoch-{k}"] /= n
     m["epoch-combined-full"] = 0 if m["epoch-drmsd-full"] == 0 else m["epoch-combined-full"] / n
-    for k in _KEPT:
+    for k in METRIC_KEYS:
         if f"n-{k}" in m:
             m[f"epoch-{k}"] = m[f"sum-{k}"] / m[f"n-{k}"] if m[f"n-{k}"] else float("nan")
-    for k in _SS:
-        if f"n-{k}" in m:                               # (a history only where the metric is reported: `-esm` reads it)
-            m.setdefault(f"epoch-history-{k}", []).append(m[f"epoch-{k}"])
+            if k in ESM_KEYS:                           # (a history only where the metric is reported: `-esm` reads it)
+                m.setdefault(f"epoch-history-{k}", []).append(m[f"epoch-{k}"])
     for h in _HISTORY:
         m[f"epoch-history-{h}"].append(m[f"epoch-{h}-full"])
     for x in _extra(m):
@@ -142,10 +133,10 @@ def update_metrics_end_of_epoch(metrics, mode):
 
 def es_value(args, metrics):
     """What early stopping, the plateau scheduler and the checkpoint policy compare, LOWER being better: `epoch-<es_metric>-full`
-    of the split `es_mode` - or, for a secondary-structure score (`-esm <split>-ss-q3`, `--eval_ss`), where higher is better, its
+    of the split `es_mode` - or, for a metric of ESM_KEYS (`-esm <split>-ss-q3`, `--eval_ss`), where higher is better, its
     negative.  Returns (value, history)."""
     m = metrics[args.es_mode]
-    if args.es_metric in _SS:
+    if args.es_metric in ESM_KEYS:
         return -m.get(f"epoch-{args.es_metric}", float("nan")), [-v for v in m.get(f"epoch-history-{args.es_metric}", [])]
     return m[f"epoch-{args.es_metric}-full"], m[f"epoch-history-{args.es_metric}"]
 
@@ -166,27 +157,29 @@ def update_loss_trackers(args, epoch_i, metrics):
 REFERENCE_CSV = False     # True: the granularity column carries upstream's literal "epoch" on every row (log.py:130)
 
 
+def log_columns(args):
+    """The keywords of `log_batch` for a run: which optional metrics' columns trail its rows."""
+    return {m.field: bool(getattr(args, m.flag, False)) for m in EVAL_METRICS}
+
+
 def prepare_log_header(args):
-    tail = ',lddt,lddt_ca' if getattr(args, "eval_lddt", False) else ''      # two trailing columns under --eval_lddt only
-    tail += ',clash' if getattr(args, "eval_clash", False) else ''            # one more, behind them, under --eval_clash only
-    tail += ',tm,gdt_ts,gdt_ha' if getattr(args, "eval_tm", False) else ''    # three more, behind those, under --eval_tm only
-    tail += ',ss_q3,ss_h,ss_e' if getattr(args, "eval_ss", False) else ''     # three more, behind those, under --eval_ss only
+    tail = "".join(f",{name}" for m in EVAL_METRICS if getattr(args, m.flag, False) for _, name in m.columns)
     if args.loss == "combined":
         return 'drmsd,ln_drmsd,rmse,rmsd,combined,lr,mode,granularity,time,speed' + tail
     return 'drmsd,ln_drmsd,rmse,rmsd,lr,mode,granularity,time,speed' + tail
 
 
-def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, lddt=False, clash=False, tm=False,
-              ss=False):
+def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False, t=None, **columns):
     """One CSV row (log.py:115-130): ten values - drmsd, ln_drmsd, rmse, rmsd, combined, lr, mode, granularity, time,
     speed; like upstream the `combined` value is written whatever the header of `prepare_log_header` lists.  One
     deliberate difference: the granularity column says "batch" for per-batch rows (upstream writes the literal "epoch"
     in both cases, log.py:130) - unless `REFERENCE_CSV` is set (`train.py --reference-csv`), which reproduces the
-    upstream column byte for byte for consumers of the reference's `.train` files.  `lddt` (`train.py --eval_lddt`): two
-    trailing values, the epoch's lddt-full and lddt-ca - nan on rows that have none (training steps never compute it).  `clash`
-    (`train.py --eval_clash`): one more trailing value, the epoch's clash-full, nan on rows that have none.  `tm`
-    (`train.py --eval_tm`): three more, the epoch's tm-ca, gdt-ts and gdt-ha, nan on rows that have none.  `ss`
-    (`train.py --eval_ss`): three more, the epoch's ss-q3, ss-h and ss-e, nan on rows that have none."""
+    upstream column byte for byte for consumers of the reference's `.train` files.  `columns` (`lddt=True`, `clash=`, `tm=`,
+    `ss=`: the fields of eval_metrics.EVAL_METRICS, as `log_columns` gives them): the values of that metric's keys trail the row
+    in the table's order - nan on rows that have none (training steps never compute most of them)."""
+    unknown = columns.keys() - {x.field for x in EVAL_METRICS}
+    if unknown:
+        raise TypeError(f"log_batch: no such column group: {sorted(unknown)}")
     t = t or time.time()
     m = metrics[mode]
     be = "epoch" if end_of_epoch else "batch"
@@ -195,14 +188,7 @@ def log_batch(log_writer, metrics, start_time, mode="valid", end_of_epoch=False,
     row = [m[f"{be}-drmsd-full"], m[f"{be}-lndrmsd-full"], np.sqrt(m[f"{be}-mse-full"]),
            m[f"{be}-rmsd-full"], m[f"{be}-combined-full"], lr, mode, label, round(t - start_time, 4),
            m.get("speed", 0)]
-    if lddt:
-        row += [m.get(f"{be}-{k}", float("nan")) for k in _LDDT]
-    if clash:
-        row += [m.get(f"{be}-{k}", float("nan")) for k in _CLASH]
-    if tm:
-        row += [m.get(f"{be}-{k}", float("nan")) for k in _TM]
-    if ss:
-        row += [m.get(f"{be}-{k}", float("nan")) for k in _SS]
+    row += [m.get(f"{be}-{k}", float("nan")) for x in EVAL_METRICS if columns.get(x.field) for k, _ in x.columns]
     log_writer.writerow(row)
 
 
@@ -214,9 +200,7 @@ def do_train_batch_logging(metrics, losses, src_seq, optimizer, args, log_writer
     lr = optimizer.param_groups[0]["lr"]
     metrics["history-lr"].append(lr)
     if dp.is_main():
-        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, lddt=bool(getattr(args, "eval_lddt", False)),
-                  clash=bool(getattr(args, "eval_clash", False)), tm=bool(getattr(args, "eval_tm", False)),
-                  ss=bool(getattr(args, "eval_ss", False)))
+        log_batch(log_writer, metrics, start_time, mode="train", end_of_epoch=False, **log_columns(args))
         if step % max(1, getattr(args, "log_wandb_step", 1) * 10) == 0:
             m = metrics["train"]
             print(f"  step {step:5d}  drmsd {m['batch-drmsd-full']:.4f}  ln {m['batch-lndrmsd-full']:.6f}  "
@@ -260,6 +244,6 @@ def do_eval_epoch_logging(metrics, mode):
     update_metrics_end_of_epoch(metrics, mode)
     if dp.is_main():
         m = metrics[mode]
-        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in _KEPT if f"epoch-{k}" in m)  # --eval_lddt, --eval_clash, --eval_tm, --eval_ss only
+        tail = "".join(f"  {k} {m[f'epoch-{k}']:.4f}" for k in METRIC_KEYS if f"epoch-{k}" in m)     # (the optional metrics only)
         print(f"  [{mode}] drmsd {m['epoch-drmsd-full']:.4f}  ln {m['epoch-lndrmsd-full']:.6f}  "
               f"rmse {np.sqrt(m['epoch-mse-full']):.4f}  rmsd {m['epoch-rmsd-full']:.4f}{tail}", flush=True)

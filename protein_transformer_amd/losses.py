@@ -16,7 +16,7 @@ from . import _lib, dp
 from .protein.Sequence import VOCAB
 from .protein.structure_utils import get_backbone_from_full_coords  # noqa: F401  (losses.py:12: importable from here too)
 from .protein.Structure import (NUM_BB_ATOMS, NUM_PREDICTED_ANGLES, NUM_PREDICTED_COORDS, SC_ANGLES_START_POS, generate_coords,
-                                nerf_backward, nerf_forward, raise_for_status)
+                                nerf_backward, nerf_forward, raise_for_status, structure_pair)
 
 
 def combine_drmsd_mse(d, mse, w=.5, lndrmsd_norm=0.02, mse_norm=0.01, log=True):
@@ -96,10 +96,7 @@ def slddt_forward_backward(crd, true_crds, seq, need_grad=True, cutoff=15.0, tem
     """Smooth lDDT loss of a batch (csrc/slddt.hip; definition in include/ptamd.h; no counterpart in the reference).
     crd, true_crds [B,L*14,3], seq [B,L].  Returns (stats [B,2] = {loss_i, score_i}, npairs [B] int64, d(loss_i)/d(crd) or None);
     a protein without an included pair has NaN statistics, npairs 0 and a zero gradient.  No host synchronisation."""
-    _lib.require_gpu(crd, true_crds, seq)
-    B, L = seq.shape
-    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
-    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    crd, true_crds, seq, B, L = structure_pair(crd, true_crds, seq)
     stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
     npairs = torch.empty(B, dtype=torch.int64, device=seq.device)
     dcrd = torch.empty_like(crd) if need_grad else None
@@ -116,10 +113,7 @@ def fape_forward_backward(crd, true_crds, seq, need_grad=True, clamp=10.0):
     crd, true_crds [B,L*14,3], seq [B,L]; `clamp` in Angstrom, float("inf") = unclamped.  Returns (stats [B,2] = {loss_i,
     nclamped_i / npairs_i}, npairs [B] int64, nclamped [B] int64, d(loss_i)/d(crd) or None); a protein without a frame or an atom,
     or with an unusable prediction, has a NaN loss and a zero gradient.  No host synchronisation."""
-    _lib.require_gpu(crd, true_crds, seq)
-    B, L = seq.shape
-    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
-    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    crd, true_crds, seq, B, L = structure_pair(crd, true_crds, seq)
     stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
     npairs = torch.empty(B, dtype=torch.int64, device=seq.device)
     nclamped = torch.empty(B, dtype=torch.int64, device=seq.device)
@@ -137,10 +131,7 @@ def kabsch_forward_backward(crd, true_crds, seq, need_grad=True):
     include/ptamd.h; the reference only evaluates it, losses.py:281-286).  crd, true_crds [B,L*14,3], seq [B,L].  Returns (stats
     [B,2] = {loss_i, n_i}, d(loss_i)/d(crd) or None); a protein with fewer than 3 present atoms, or with a NaN / infinite predicted
     coordinate on a present atom, has a NaN loss and a zero gradient.  One launch, no workspace, no host synchronisation."""
-    _lib.require_gpu(crd, true_crds, seq)
-    B, L = seq.shape
-    crd, true_crds, seq = crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
-    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    crd, true_crds, seq, B, L = structure_pair(crd, true_crds, seq)
     stats = torch.empty(B, 2, dtype=torch.float32, device=seq.device)
     dcrd = torch.empty_like(crd) if need_grad else None
     rc = _lib.lib().ptamd_kabsch_loss_fwd_bwd(_lib.ptr(crd), _lib.ptr(true_crds), _lib.ptr(seq), B, L, _lib.ptr(stats),
@@ -208,10 +199,8 @@ def rename_symmetric(crd, true_crds, seq, true_ang=None):
     crd, true_crds [B,L*14,3], seq [B,L], true_ang [B,L,24] (cos, sin interleaved) or None.  Returns (true_crds', true_ang' or
     None, swapped [B,L] int32, cost [B,L,2] = {orig, alt}): new tensors, the inputs are untouched.  A constant for the gradient.
     No host synchronisation."""
-    _lib.require_gpu(crd, true_crds, seq, true_ang)
-    B, L = seq.shape
-    crd, true_crds, seq = crd.detach().float().contiguous(), true_crds.float().contiguous(), seq.contiguous()
-    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    _lib.require_gpu(true_ang)
+    crd, true_crds, seq, B, L = structure_pair(crd.detach(), true_crds, seq)
     crd_out = torch.empty_like(true_crds)
     ang_out = None
     if true_ang is not None:
@@ -230,7 +219,7 @@ def rename_symmetric(crd, true_crds, seq, true_ang=None):
 
 # ----------------------------------------------------------------------------- the extra structural losses
 # All the host code knows about a structural loss beside the dRMSD family (`train.py -l <name>`; the name is also its keyword in
-# `batch_loss` and `LossReport` and its key in `LossReport.wait()`).  run(crd, true_crds, seq, need_grad, params) -> (per-protein
+# `batch_loss`, its field in REPORT_FIELDS and its key in `LossReport.wait()`).  run(crd, true_crds, seq, need_grad, params) -> (per-protein
 # loss [B], its gradient d/d(crd) or None); params(args): as batch_loss takes them; check(params): the parser's complaint or None.
 ExtraLoss = namedtuple("ExtraLoss", "name run params check backbone_message")
 
@@ -406,14 +395,23 @@ def _pinned(kind, n, dtype, device):
     return buf
 
 
-# A CHANNEL of a report: per-protein fp32 values [B], reported as their mean over the proteins of the global batch that have a
-# finite one.  A field of k columns carries k channels (`lddt`, of --eval_lddt: two); field -> the `wait()` keys of its columns:
-# These three are the fixed part of every report and of the reduced vector, whose slots stay where they have always been; an
-# extra loss that came later (`kabsch`) travels in the tail below.
-_CHANNEL_FIELDS = {"lddt": ("lddt", "lddt-ca"), "slddt": ("slddt",), "fape": ("fape",)}
+# THE FIELDS of a report beside stats, mse, status and rmsd, in the order they travel in: per-protein fp32 values [B] or [B,k], every
+# column reported as its mean over the proteins of the global batch that have a finite one.  name, the `wait()` keys of its columns,
+# and where it lies - the one wire fact, which nothing outside this section needs to know: the FIXED fields are part of every
+# report (their keys are always in `wait()`, their slots always in the reduced vector, where they have always been); whatever came
+# later lies in the TAIL behind them - `kabsch` too, an extra loss like `slddt` and `fape` - and only in the reports of callers that
+# ASK for it.  Asking is the field being a key of the mapping a caller passes, with None where it has no value; every rank of a job
+# asks for the same fields, a rank with an empty shard included, so their vectors have one length.  A report nobody asked a tail
+# field of has exactly the layout, the keys and the size it had before there was one.
+ReportField = namedtuple("ReportField", "name keys fixed")
+REPORT_FIELDS = (ReportField("lddt", ("lddt", "lddt-ca"), True), ReportField("slddt", ("slddt",), True),
+                 ReportField("fape", ("fape",), True), ReportField("clash", ("clash",), False),
+                 ReportField("tm", ("tm-ca", "gdt-ts", "gdt-ha"), False), ReportField("kabsch", ("kabsch",), False),
+                 ReportField("ss", ("ss-q3", "ss-h", "ss-e"), False))
+REPORT_KEYS = {f.name: f.keys for f in REPORT_FIELDS}
 _MEANS = ("drmsd", "lndrmsd", "drmsd-bb", "lndrmsd-bb")        # stats[:, :4], reported as their means over the proteins
 _NO_REPORT = {**dict.fromkeys(_MEANS, 0.0), "rmsd": None, "n_proteins": 0, "status": 0, "n_res": None, "mse": None,
-              **{key: None for keys in _CHANNEL_FIELDS.values() for key in keys}}
+              **{key: None for f in REPORT_FIELDS if f.fixed for key in f.keys}}
 
 
 def _take(fields):
@@ -439,46 +437,26 @@ def finite_mean(x):
 
 
 @functools.lru_cache(maxsize=None)
-def _local_layout(B, present):
-    """({field of `present`: its slice}, size): stats, mse, status, rmsd keep their room when absent, a channel field takes none."""
+def _local_layout(B, present, hollow):
+    """({name of `present` or `hollow`: its slice}, size): stats, mse, status, rmsd keep their room when absent; a field of
+    REPORT_FIELDS takes room where it is `present`, and an empty slice where it was asked for without a value (`hollow`)."""
     at, size = _take([("stats", 8 * B), ("mse", 6), ("status", 1), ("rmsd", B)]
-                     + [(field, len(keys) * B) for field, keys in _CHANNEL_FIELDS.items() if field in present])
-    return {name: at[name] for name in present}, size
-
-
-# The TAIL of a report: channel fields that lie behind everything above - behind the channel fields of a single process, behind
-# VECTOR_SLOTS under data parallelism - and only in the reports of callers that ASK for them (`tail`: {field: [B] or [B,k], or
-# None for a rank that has no value}; every rank of a job asks for the same fields, a rank with an empty shard included, so their
-# vectors have one length).  A report nobody asked a tail of has exactly the layout, the keys and the size it had before there
-# was one.  field -> the `wait()` keys of its columns:
-_TAIL_FIELDS = {"clash": ("clash",), "tm": ("tm-ca", "gdt-ts", "gdt-ha")}
-# ... and behind those the extra losses that have no channel in the fixed part (`kabsch`): one column each, asked for in the runs
-# whose loss it is (LossReport's keyword with_<name>)
-TAIL_LOSSES = tuple(name for name in EXTRA_LOSSES if name not in _CHANNEL_FIELDS)
-# ... and behind those the evaluation metrics that came after them, in a registry of their own so that the two above stay what they
-# are: `ss` (--eval_ss), three columns
-_TAIL_METRICS = {"ss": ("ss-q3", "ss-h", "ss-e")}
-_TAIL_KEYS = {**_TAIL_FIELDS, **{name: (name,) for name in TAIL_LOSSES}, **_TAIL_METRICS}
-
-
-def _tail_layout(tail, start, width):
-    """{field asked for: its slice behind `start`}, end; width(field, tensor or None) -> words."""
-    at, size = _take([(field, width(field, t)) for field, t in (tail or {}).items()])
-    return {field: slice(start + s.start, start + s.stop) for field, s in at.items()}, start + size
+                     + [(f.name, len(f.keys) * B if f.name in present else 0) for f in REPORT_FIELDS if f.name in present + hollow])
+    return {name: s for name, s in at.items() if name in present + hollow}, size
 
 
 def pack_local(stats=None, mse=None, status=None, rmsd=None, channels=None, alloc=torch.empty, tail=None):
     """What a single process reports, in one fp32 buffer: stats [B,8], the six MSE sums, the status word (int32[1], as raw bits),
-    rmsd [B] and the `channels` ({field of _CHANNEL_FIELDS: [B] or [B,k]}), each of them or None; behind them the `tail` (above).
-    One (asynchronous) copy per field into `alloc(size)` (default: a host tensor); returns the buffer and its layout (B, {field
-    that was passed: slice}) - a tail field that was asked for without a value has an empty slice."""
-    given = {k: t for k, t in dict(stats=stats, mse=mse, status=status, rmsd=rmsd, **(channels or {})).items() if t is not None}
-    tailed = {field: t for field, t in (tail or {}).items() if t is not None}
-    B = next((t.shape[0] for name, t in {**given, **tailed}.items() if name not in ("mse", "status")), 0)
-    at, size = _local_layout(B, tuple(given))
-    if tail:
-        tail_at, size = _tail_layout(tail, size, lambda field, t: 0 if t is None else len(_TAIL_KEYS[field]) * B)
-        at, given = {**at, **tail_at}, {**given, **tailed}
+    rmsd [B], each of them or None, and the fields of REPORT_FIELDS ({field: [B] or [B,k], or None}; `channels` and `tail` are one
+    mapping, in two keywords for the callers that tell fixed fields from tail fields).  One (asynchronous) copy per field into
+    `alloc(size)` (default: a host tensor); returns the buffer and its layout (B, {field that was passed: slice}) - a tail field
+    that was asked for without a value has an empty slice, a fixed field without one is left out."""
+    fields = {**(channels or {}), **(tail or {})}
+    given = {k: t for k, t in dict(stats=stats, mse=mse, status=status, rmsd=rmsd).items() if t is not None}
+    given.update({f.name: fields[f.name] for f in REPORT_FIELDS if fields.get(f.name) is not None})
+    hollow = tuple(f.name for f in REPORT_FIELDS if not f.fixed and f.name in fields and fields[f.name] is None)
+    B = next((t.shape[0] for name, t in given.items() if name not in ("mse", "status")), 0)
+    at, size = _local_layout(B, tuple(given), hollow)
     buf = alloc(size)
     for name, t in given.items():
         dst = buf.view(torch.int32) if name == "status" else buf
@@ -500,39 +478,33 @@ def unpack_local(host, layout, n_res=None):
         out["status"] = int(host[at["status"]].view(np.int32)[0])
     if "rmsd" in at and B:
         out["rmsd"] = float(np.mean(host[at["rmsd"]].astype(np.float64)))
-    for field, keys in _CHANNEL_FIELDS.items():
-        if field in at:
-            values = host[at[field]].reshape(B, len(keys))
-            out.update({key: finite_mean(values[:, k]) for k, key in enumerate(keys)})
-    for field, keys in _TAIL_KEYS.items():
-        if field in at:                               # asked for: the keys exist, None when no value was passed
-            values = host[at[field]].reshape(-1, len(keys))
-            out.update({key: finite_mean(values[:, k]) if len(values) else None for k, key in enumerate(keys)})
+    for f in REPORT_FIELDS:
+        if f.name in at:                              # passed or asked for: the keys exist, None when no value was passed
+            values = host[at[f.name]].reshape(-1, len(f.keys))
+            out.update({key: finite_mean(values[:, k]) if len(values) else None for k, key in enumerate(f.keys)})
     return out
 
 
-# The fp64 vector a rank adds to the SUM reduction.  sums: of stats[:, :4]; ranks_counted: the ranks that passed a residue count
-# (0: n_res stays None like on one rank); a channel field: its `finite_sums` (zeros on a rank that does not report it).
-VECTOR_SLOTS, VECTOR_SIZE = _take([("sums", 4), ("proteins", 1), ("rmsd_sum", 1), ("mse", 6), ("status_bits", 4), ("residues", 1),
-                                   ("rmsd_proteins", 1), ("ranks_counted", 1)]
-                                  + [(field, 2 * len(keys)) for field, keys in _CHANNEL_FIELDS.items()])
+@functools.lru_cache(maxsize=None)
+def _vector_layout(asked=frozenset()):
+    """({slot: slice}, size) of the fp64 vector a rank adds to the SUM reduction, in a job that asks for the fields `asked`.  sums: of
+    stats[:, :4]; ranks_counted: the ranks that passed a residue count (0: n_res stays None like on one rank); a field of
+    REPORT_FIELDS: its `finite_sums` (zeros on a rank without a value).  The fixed fields have their slots whoever asks, a tail
+    field when it was ASKED for - the length depends on that alone, so an empty shard adds a vector as long as the others'."""
+    return _take([("sums", 4), ("proteins", 1), ("rmsd_sum", 1), ("mse", 6), ("status_bits", 4), ("residues", 1),
+                  ("rmsd_proteins", 1), ("ranks_counted", 1)]
+                 + [(f.name, 2 * len(f.keys)) for f in REPORT_FIELDS if f.fixed or f.name in asked])
 
 
-def _vector_tail(tail):
-    """({field asked for: its slice behind VECTOR_SLOTS}, the vector's size): a field's `finite_sums`, whether or not the rank has a
-    value - the length depends on what was ASKED alone, so an empty shard adds a vector as long as the others'."""
-    return _tail_layout(tail, VECTOR_SIZE, lambda field, t: 2 * len(_TAIL_KEYS[field]))
+VECTOR_SLOTS, VECTOR_SIZE = _vector_layout()         # what every vector starts with: the tail's slots lie behind these
 
 
 def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, channels=None, device=None, tail=None):
-    """This rank's vector of VECTOR_SLOTS (arguments as `pack_local`; an empty shard passes None for everything - and, in `tail`,
-    None for every field the job asks for), with the tail's slots behind them.  No host sync."""
-    S = VECTOR_SLOTS
-    tail_at, size = _vector_tail(tail)
+    """This rank's vector (arguments as `pack_local`; an empty shard passes None for everything - and None for every tail field
+    the job asks for).  No host sync."""
+    fields = {**(channels or {}), **(tail or {})}
+    S, size = _vector_layout(frozenset(fields))
     v = torch.zeros(size, dtype=torch.float64, device=device)
-    for field, at in tail_at.items():
-        if tail[field] is not None:
-            v[at] = finite_sums(tail[field])
     if stats is not None:
         v[S["sums"]], v[S["proteins"]] = stats[:, :4].double().sum(0), stats.shape[0]
     if rmsd is not None:
@@ -542,16 +514,17 @@ def reduce_vector(stats=None, mse=None, status=None, rmsd=None, n_res=None, chan
     if status is not None:
         v[S["status_bits"]] = ((status.to(torch.int64) >> torch.arange(4, device=status.device)) & 1).double()
     v[S["residues"]], v[S["ranks_counted"]] = float(n_res or 0), 0.0 if n_res is None else 1.0
-    for field, t in (channels or {}).items():
+    for field, t in fields.items():
         if t is not None:
             v[S[field]] = finite_sums(t)
     return v
 
 
 def unpack_global(v, passed=(), tail=()):
-    """The `LossReport.wait()` dictionary from the REDUCED vector (numpy fp64), the same on every rank.  A channel stays None unless
+    """The `LossReport.wait()` dictionary from the REDUCED vector (numpy fp64), the same on every rank.  A column stays None unless
     a protein of the global batch has a value (a rank with an empty shard reads it too) or this rank `passed` its field (then NaN).
-    `tail`: the tail fields the job asked for, in the order of `reduce_vector` - their keys exist then, under the same rule."""
+    `tail`: the fields the job asked for - the keys of the tail fields among them exist then, under the same rule."""
+    S = _vector_layout(frozenset(tail))[0]
     one = {name: v[at][0] for name, at in VECTOR_SLOTS.items()}          # (the first entry of every slot: for the one-entry slots)
     out = dict(_NO_REPORT, n_proteins=int(one["proteins"]), mse=v[VECTOR_SLOTS["mse"]],
                status=sum(1 << k for k, n in enumerate(v[VECTOR_SLOTS["status_bits"]]) if n > 0),
@@ -559,14 +532,11 @@ def unpack_global(v, passed=(), tail=()):
     out.update(zip(_MEANS, v[VECTOR_SLOTS["sums"]] / max(one["proteins"], 1.0)))
     if one["rmsd_proteins"] > 0:
         out["rmsd"] = one["rmsd_sum"] / one["rmsd_proteins"]
-    for field, keys in _CHANNEL_FIELDS.items():
-        total, count = v[VECTOR_SLOTS[field]].reshape(2, -1)
-        out.update({key: total[k] / count[k] if count[k] > 0 else float("nan")
-                    for k, key in enumerate(keys) if count[k] > 0 or field in passed})
-    for field, at in _vector_tail(dict.fromkeys(tail))[0].items():
-        total, count = v[at].reshape(2, -1)
-        out.update({key: total[k] / count[k] if count[k] > 0 else float("nan") if field in passed else None
-                    for k, key in enumerate(_TAIL_KEYS[field])})
+    for f in REPORT_FIELDS:
+        if f.name in S:
+            total, count = v[S[f.name]].reshape(2, -1)
+            out.update({key: total[k] / count[k] if count[k] > 0 else float("nan") if f.name in passed else None
+                        for k, key in enumerate(f.keys)})
     return out
 
 
@@ -585,37 +555,25 @@ class LossReport:
     A rank whose shard is empty passes None for everything and still takes part in the reduction.
     """
 
-    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, clash=None, with_clash=False,
-                 tm=None, with_tm=False, kabsch=None, with_kabsch=False, ss=None, with_ss=False, lddt=None, slddt=None, fape=None):
-        """`lddt`: per-protein scores [B,2] of eval_metrics.lddt_batch (evaluation under --eval_lddt) or None.
-        `slddt`, `fape`: the per-protein losses [B] of batch_loss under that extra loss (`-l slddt`, `-l fape`) or None.
-        `clash`: the per-protein clash losses [B] (`--clash_weight`, `--eval_clash`) or None; `with_clash`: the job reports them -
-        true on EVERY rank then, also on one whose shard is empty and has none: the report carries the tail for them, and `wait()`
-        the key `clash`.
-        `tm`: the per-protein scores [B,3] of eval_metrics.tm_batch (evaluation under --eval_tm) or None; `with_tm` as `with_clash`:
-        one more tail field of three columns, and `wait()` the keys `tm-ca`, `gdt-ts`, `gdt-ha`.
-        `kabsch`: the per-protein losses [B] of batch_loss under `-l kabsch` or None; `with_kabsch` as `with_clash` (true on every
-        rank of such a run): one more tail field, and `wait()` the key `kabsch`, reduced like `slddt` and `fape`.
-        `ss`: the per-protein scores [B,3] of eval_metrics.ss_batch (evaluation under --eval_ss) or None; `with_ss` as `with_clash`:
-        the last tail field, three columns, and `wait()` the keys `ss-q3`, `ss-h`, `ss-e`."""
+    def __init__(self, device, stats=None, status=None, mse_sums_local=None, rmsd=None, n_res=None, fields=None):
+        """`fields`: {field of REPORT_FIELDS: its per-protein values [B] or [B,k], or None} - what the job reports beside the
+        arguments in front.  A key is there on EVERY rank of the job, with None on one that has no value (an empty shard)."""
+        fields = dict(fields or {})
+        if not REPORT_KEYS.keys() >= fields.keys():
+            raise ValueError(f"not a field of a loss report: {sorted(fields.keys() - REPORT_KEYS.keys())}")
         self.world, self.n_res = dp.world_size(), n_res
-        channels = {"lddt": lddt, "slddt": slddt, "fape": fape}
-        tail = {**({"clash": clash} if with_clash or clash is not None else {}),
-                **({"tm": tm} if with_tm or tm is not None else {}),
-                **({"kabsch": kabsch} if with_kabsch or kabsch is not None else {}),
-                **({"ss": ss} if with_ss or ss is not None else {})} or None
         if self.world == 1:
-            buf, layout = pack_local(stats, mse_sums_local, status, rmsd, channels,
-                                     alloc=lambda n: _pinned("report32", n, torch.float32, device), tail=tail)
+            buf, layout = pack_local(stats, mse_sums_local, status, rmsd, fields,
+                                     alloc=lambda n: _pinned("report32", n, torch.float32, device))
             self.global_mse_sums = mse_sums_local
             self._unpack = lambda: unpack_local(buf.numpy(), layout, n_res)
         else:
-            v = dp.all_reduce_sum_(reduce_vector(stats, mse_sums_local, status, rmsd, n_res, channels, device, tail=tail))
+            v = dp.all_reduce_sum_(reduce_vector(stats, mse_sums_local, status, rmsd, n_res, fields, device))
             self.global_mse_sums = v[VECTOR_SLOTS["mse"]].float()
             buf = _pinned("report64", v.numel(), torch.float64, device)
             buf.copy_(v, non_blocking=True)
-            passed = {field for field, t in {**channels, **(tail or {})}.items() if t is not None}
-            self._unpack = lambda: unpack_global(buf.numpy().copy(), passed, tuple(tail or ()))
+            passed = {field for field, t in fields.items() if t is not None}
+            self._unpack = lambda: unpack_global(buf.numpy().copy(), passed, tuple(fields))
         self._event = torch.cuda.Event()
         self._event.record()
 

@@ -28,6 +28,15 @@ def raise_for_status(word, theta_is_error=True):
         raise AssertionError("theta must be in radians and in [-pi, pi] (Structure.py:42)")
 
 
+def structure_pair(crd, true_crds, seq):
+    """What every kernel wrapper over a prediction and its truth starts with: crd, true_crds [B,L*14,3] and seq [B,L], device
+    tensors -> (crd, true_crds, seq, B, L), the coordinates as contiguous fp32, the shapes checked."""
+    _lib.require_gpu(crd, true_crds, seq)
+    B, L = seq.shape
+    assert crd.shape == (B, L * NUM_PREDICTED_COORDS, 3) and true_crds.shape == crd.shape
+    return crd.float().contiguous(), true_crds.float().contiguous(), seq.contiguous(), B, L
+
+
 _STATUS_POOL = {}
 
 

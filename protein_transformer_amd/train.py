@@ -25,13 +25,12 @@ import torch
 
 from . import dp
 from .dataset import MAX_SEQ_LEN, DevicePrefetcher, prepare_dataloaders
-from .eval_metrics import clash_batch, kabsch_rmsd_batch, lddt_batch, ss_batch, tm_batch
-from .log import _SS as SS_KEYS
+from .eval_metrics import ESM_KEYS, EVAL_METRICS, kabsch_rmsd_batch
 from .log import (EarlyStoppingCondition, do_eval_batch_logging, do_eval_epoch_logging, do_train_batch_logging, es_value,
-                  init_metrics, log_batch, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
+                  init_metrics, log_batch, log_columns, prepare_log_header, reset_metrics_for_epoch, update_loss_trackers,
                   update_metrics_end_of_epoch)
 from .losses import (CLASH_BACKBONE_MESSAGE, CLASH_NO_STRUCTURE_MESSAGE, CLASH_TOLERANCE, EXTRA_LOSSES, RENAME_BACKBONE_MESSAGE,
-                     RENAME_NO_STRUCTURE_MESSAGE, TAIL_LOSSES, BatchLoss, LossReport, batch_loss, clash_check, combine_drmsd_mse,
+                     RENAME_NO_STRUCTURE_MESSAGE, REPORT_KEYS, BatchLoss, LossReport, batch_loss, clash_check, combine_drmsd_mse,
                      mse_grad, mse_sums, predicted_coords)
 from .models.convolutional_encoder import ConvEncoderOnlyTransformer
 from .models.encoder_only import EncoderOnlyTransformer
@@ -165,20 +164,19 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
     backbone = bool(getattr(args, "backbone_loss", False)) and need_drmsd
     if extra is not None and backbone:
         raise ValueError(extra.backbone_message)
-    want_lddt = eval_mode and bool(getattr(args, "eval_lddt", False))
-    want_tm = eval_mode and bool(getattr(args, "eval_tm", False))
-    want_ss = eval_mode and bool(getattr(args, "eval_ss", False))
     rename = bool(getattr(args, "rename_symmetric", False))
     if rename and (backbone or not need_drmsd):
         raise ValueError(RENAME_BACKBONE_MESSAGE if backbone else RENAME_NO_STRUCTURE_MESSAGE)
     clash_w, clash_tol = float(getattr(args, "clash_weight", 0.0)), float(getattr(args, "clash_tolerance", CLASH_TOLERANCE))
     if clash_w > 0 and (backbone or not need_drmsd):
         raise ValueError(CLASH_BACKBONE_MESSAGE if backbone else CLASH_NO_STRUCTURE_MESSAGE)
-    want_clash = clash_w > 0 or (eval_mode and bool(getattr(args, "eval_clash", False)))
+    # the optional metrics are evaluation's; the clash term is reported by every step that trains on it, too
+    wanted = [x for x in EVAL_METRICS if (eval_mode and getattr(args, x.flag, False)) or (x.field == "clash" and clash_w > 0)]
+    fields = dict.fromkeys(x.field for x in wanted)        # asked for on every rank; None: this one (an empty shard) has no value
     structure = need_drmsd and not empty
     compact = backbone and not eval_mode       # a training step under --backbone_loss builds no side chains: N, CA, C alone
     res = BatchLoss()
-    grad = sums = rmsd = lddt = clash = tm = ss = None
+    grad = sums = rmsd = None
     if structure:
         # the structure (and the renaming) come first: the MSE, the RMSD and the lDDT below see the truth the losses saw
         kw = dict(do_backward=do_backwards and (compact or not backbone), backbone_only=compact, rename_symmetric=rename,
@@ -188,7 +186,7 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         if clash_w > 0:                        # the term trains: batch_loss runs it on the gradient's way
             kw["clash"] = (clash_w, clash_tol)
         res = batch_loss(pred, tgt_crds, src_seq, **kw)
-        grad, clash, tgt_crds, tgt_ang = res.grad, res.clash, res.true_crds, res.true_ang
+        grad, tgt_crds, tgt_ang = res.grad, res.true_crds, res.true_ang
         if backbone and not compact and do_backwards:      # evaluation that also back-propagates: the gradient is the backbone's
             grad = batch_loss(pred, tgt_crds, src_seq, do_backward=True, backbone_only=True).grad
     if not empty:
@@ -197,20 +195,12 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
         if return_rmsd:                        # (the compact backbone of a training step does: all atoms, for the RMSD alone)
             crd = predicted_coords(pred, src_seq, status=res.status)[0] if compact else res.crd
             rmsd = kabsch_rmsd_batch(crd, tgt_crds, src_seq)
-        if want_lddt:
-            lddt = lddt_batch(res.crd, tgt_crds, src_seq)[0]
-        if want_clash and clash is None:       # --eval_clash without the training term
-            clash = clash_batch(res.crd, src_seq, clash_tol)[0]
-        if want_tm:                            # (--rename_symmetric renames side-chain atoms: the C-alphas are the same)
-            tm = tm_batch(res.crd, tgt_crds, src_seq)[0]
-        if want_ss:                            # (nor does the renaming touch N, CA, C, O)
-            ss = ss_batch(res.crd, tgt_crds, src_seq)[0]
-    report = LossReport(dev, stats=res.stats, status=res.status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, lddt=lddt,
-                        **({extra.name: res.per_protein} if extra is not None else {}),
-                        **({f"with_{extra.name}": True} if extra is not None and extra.name in TAIL_LOSSES else {}),
-                        **({"clash": clash, "with_clash": True} if want_clash else {}),
-                        **({"tm": tm, "with_tm": True} if want_tm else {}),
-                        **({"ss": ss, "with_ss": True} if want_ss else {}))
+        for x in wanted:                       # (the clash term that trained has its value: --eval_clash launches nothing more)
+            trained = x.field == "clash" and res.clash is not None
+            fields[x.field] = res.clash if trained else x.run(res.crd, tgt_crds, src_seq, args)
+    if extra is not None:
+        fields[extra.name] = res.per_protein
+    report = LossReport(dev, stats=res.stats, status=res.status, mse_sums_local=sums, rmsd=rmsd, n_res=n_res, fields=fields)
     if do_backwards and not empty:
         w = args.combined_drmsd_weight
         if args.loss == "mse":
@@ -251,16 +241,12 @@ def get_losses(args, pred, tgt_ang, tgt_crds, src_seq, pool=None, log=True, do_b
            "mse-sc": m_loss_sc, "rmsd-full": rmsd_loss}
     if extra is not None:
         out[f"{extra.name}-full"] = loss
-    if want_clash:      # --clash_weight, --eval_clash: one more key, the mean over the proteins of the GLOBAL batch that have a value
+    if "clash" in fields:       # its key stands in front of the other metrics', and the term that trained is part of the loss
         out["clash-full"] = channel("clash")
         if clash_w > 0:
             out["loss"] = loss + clash_w * out["clash-full"]
-    if want_lddt:       # --eval_lddt: two more keys, means over the proteins of the GLOBAL batch that have a score
-        out["lddt-full"], out["lddt-ca"] = channel("lddt"), channel("lddt-ca")
-    if want_tm:         # --eval_tm: three more keys, means over the proteins of the GLOBAL batch that have a score
-        out["tm-ca"], out["gdt-ts"], out["gdt-ha"] = channel("tm-ca"), channel("gdt-ts"), channel("gdt-ha")
-    if want_ss:         # --eval_ss: three more keys, means over the proteins of the GLOBAL batch that have a score
-        out["ss-q3"], out["ss-h"], out["ss-e"] = channel("ss-q3"), channel("ss-h"), channel("ss-e")
+    for x in wanted:            # per column one more key: the mean over the proteins of the GLOBAL batch that have a finite value
+        out.update({key: channel(k) for (key, _), k in zip(x.columns, REPORT_KEYS[x.field])})
     if host["n_res"] is not None:
         out["n-residues"] = host["n_res"]                      # residues of the GLOBAL batch (speed meter, log.py)
     return out
@@ -283,7 +269,7 @@ def eval_epoch(model, validation_data, device, args, metrics, mode="valid", pool
 def train(model, metrics, training_data, train_eval_loader, validation_datasets, test_data, optimizer, device, args,
           log_writer, scheduler, drmsd_worker_pool):
     """ Model training control loop (train.py:138-186). """
-    columns = {k: getattr(args, f"eval_{k}", False) for k in ("lddt", "clash", "tm", "ss")}      # log_batch: the rows' trailing columns
+    columns = log_columns(args)                # log_batch: the rows' trailing columns
     for epoch_i in range(START_EPOCH, args.epochs):
         if dp.is_main():
             print(f'[ Epoch {epoch_i} ]')
@@ -558,8 +544,9 @@ class _Parser(argparse.ArgumentParser):
             problem = clash_check(a.clash_weight, a.clash_tolerance)
         if not problem and a.clash_weight > 0:
             problem = CLASH_BACKBONE_MESSAGE if a.backbone_loss else CLASH_NO_STRUCTURE_MESSAGE if a.loss == "mse" else None
-        if not problem and early_stopping_target(a)[1] in SS_KEYS and not a.eval_ss:
-            problem = SS_ESM_MESSAGE
+        es_metric = early_stopping_target(a)[1]
+        if not problem and any(m.esm and es_metric in dict(m.columns) and not getattr(a, m.flag) for m in EVAL_METRICS):
+            problem = SS_ESM_MESSAGE                # (the one metric that is a target)
         if problem:
             self.error(problem)
         return a
@@ -570,7 +557,7 @@ def early_stopping_target(args):
     (Loss names carry no hyphen - `slddt`, `fape`, `kabsch` - because of this split.)  The secondary-structure scores of
     `--eval_ss` are metrics too, as `<split>-ss-q3`, `-ss-h`, `-ss-e`: higher is better there (log.es_value)."""
     target = args.early_stopping_metric or f"train-{args.loss}"
-    for key in SS_KEYS:
+    for key in ESM_KEYS:
         if target.endswith("-" + key):
             return target[:-len(key) - 1], key
     return tuple(target.rsplit("-", 1))

@@ -106,7 +106,8 @@ def test_defaults_and_no_cpu_path(built_lib):
     assert list(inspect.signature(eval_metrics.clash_batch).parameters) == ["crd", "seq", "tolerance"]
     assert inspect.signature(losses.batch_loss).parameters["clash"].default is None            # today's calls are untouched
     report = inspect.signature(losses.LossReport.__init__).parameters
-    assert report["clash"].default is None and report["with_clash"].default is False
+    assert report["fields"].default is None and "clash" not in report     # asked for without a value: fields={"clash": None}
+    assert losses.REPORT_KEYS["clash"] == ("clash",)
     with pytest.raises(RuntimeError, match="device tensors only"):      # a missing GPU is an error, never a CPU fall-back
         losses.clash_forward_backward(torch.zeros(1, 28, 3), torch.zeros(1, 2, dtype=torch.int64))
     with pytest.raises(RuntimeError, match="device tensors only"):

@@ -141,8 +141,8 @@ def test_host_mirror_signatures_and_no_cpu_path(built_lib):
     assert list(sig) == ["crd", "true_crds", "seq", "need_grad", "clamp"]
     assert sig["clamp"].default == 10.0 and sig["need_grad"].default is True
     assert inspect.signature(losses.batch_loss).parameters["fape"].default is None        # today's calls are untouched
-    params = list(inspect.signature(losses.LossReport.__init__).parameters)
-    assert params[-1] == "fape" and params[-2] == "slddt"                                 # behind the existing ones
-    assert inspect.signature(losses.LossReport.__init__).parameters["fape"].default is None
+    fixed = [f.name for f in losses.REPORT_FIELDS if f.fixed]
+    assert fixed[-1] == "fape" and fixed[-2] == "slddt"                                   # behind the existing ones
+    assert inspect.signature(losses.LossReport.__init__).parameters["fields"].default is None      # (fields={"fape": values})
     with pytest.raises(RuntimeError, match="device tensors only"):      # a missing GPU is an error, never a CPU fall-back
         losses.fape_forward_backward(torch.zeros(1, 28, 3), torch.zeros(1, 28, 3), torch.zeros(1, 2, dtype=torch.int64))

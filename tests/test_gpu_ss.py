@@ -191,12 +191,12 @@ def test_get_losses_reports_the_three_scores(monkeypatch):
     without the flag the dictionary is, key for key and bit for bit, the one of before and the kernel is never called; training
     steps never carry the keys."""
     from test_gpu_clash_train import _setup
-    from protein_transformer_amd import train
+    from protein_transformer_amd import eval_metrics, train
     from protein_transformer_amd.eval_metrics import ss_batch
     from protein_transformer_amd.losses import angles_forward, finite_mean
     from protein_transformer_amd.protein.Structure import nerf_forward
-    calls = []
-    monkeypatch.setattr(train, "ss_batch", lambda *a, **k: calls.append(1) or ss_batch(*a, **k))
+    calls = []               # (get_losses reaches the kernel through the record of eval_metrics.EVAL_METRICS, which calls this name)
+    monkeypatch.setattr(eval_metrics, "ss_batch", lambda *a, **k: calls.append(1) or ss_batch(*a, **k))
     model, _, args, batch = _setup("drmsd")
     seq, ang, crd = (t.to(DEV) for t in batch)
     model.eval()

@@ -196,8 +196,9 @@ def test_host_mirror_signatures_and_no_cpu_path(built_lib):
     assert list(sig) == ["crd", "true_crds", "seq", "need_grad"] and sig["need_grad"].default is True
     assert inspect.signature(losses.batch_loss).parameters["kabsch"].default is None          # today's calls are untouched
     report = inspect.signature(losses.LossReport.__init__).parameters
-    assert report["kabsch"].default is None and report["with_kabsch"].default is False
-    assert list(losses.EXTRA_LOSSES) == ["slddt", "fape", "kabsch"] and losses.TAIL_LOSSES == ("kabsch",)
+    assert report["fields"].default is None and "kabsch" not in report    # asked for without a value: fields={"kabsch": None}
+    assert list(losses.EXTRA_LOSSES) == ["slddt", "fape", "kabsch"] and losses.REPORT_KEYS["kabsch"] == ("kabsch",)
+    assert [f.name for f in losses.REPORT_FIELDS if not f.fixed and f.name in losses.EXTRA_LOSSES] == ["kabsch"]      # in the tail
     with pytest.raises(RuntimeError, match="device tensors only"):      # a missing GPU is an error, never a CPU fall-back
         losses.kabsch_forward_backward(torch.zeros(1, 28, 3), torch.zeros(1, 28, 3), torch.zeros(1, 2, dtype=torch.int64))
     with pytest.raises(AssertionError, match="-l kabsch is an all-atom loss"):

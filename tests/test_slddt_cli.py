@@ -133,7 +133,8 @@ def test_host_mirror_signatures_and_no_cpu_path(built_lib):
     assert list(sig) == ["crd", "true_crds", "seq", "need_grad", "cutoff", "temperature"]
     assert sig["cutoff"].default == 15.0 and sig["temperature"].default == 1.0
     assert inspect.signature(losses.batch_loss).parameters["slddt"].default is None       # today's calls are untouched
-    assert inspect.signature(losses.LossReport.__init__).parameters["slddt"].default is None
+    assert inspect.signature(losses.LossReport.__init__).parameters["fields"].default is None      # (fields={"slddt": values})
+    assert losses.REPORT_KEYS["slddt"] == ("slddt",)
     assert losses.VECTOR_SIZE == 27 and losses.VECTOR_SLOTS == {        # the reduced vector: every slot where it has always been
         "sums": slice(0, 4), "proteins": slice(4, 5), "rmsd_sum": slice(5, 6), "mse": slice(6, 12), "status_bits": slice(12, 16),
         "residues": slice(16, 17), "rmsd_proteins": slice(17, 18), "ranks_counted": slice(18, 19), "lddt": slice(19, 23),

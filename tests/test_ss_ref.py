@@ -168,7 +168,10 @@ def test_header_and_rows_without_the_flag_are_byte_identical():
 
 def test_rows_with_the_flag_the_epoch_line_and_early_stopping(capsys):
     from protein_transformer_amd import log
-    assert log._SS == KEYS and log._KEPT[-3:] == KEYS and log._OPTIONAL[-3:] == log._TM
+    from protein_transformer_amd.eval_metrics import ESM_KEYS, EVAL_METRICS, METRIC_KEYS
+    assert [m.field for m in EVAL_METRICS] == ["lddt", "clash", "tm", "ss"]              # the log's order: ss behind every older one
+    assert tuple(k for k, _ in EVAL_METRICS[-1].columns) == KEYS and ESM_KEYS == KEYS and METRIC_KEYS[-3:] == KEYS
+    assert METRIC_KEYS[-6:-3] == tuple(k for k, _ in EVAL_METRICS[2].columns) == ("tm-ca", "gdt-ts", "gdt-ha")
     scored = {"ss-q3": 0.75, "ss-h": 0.5, "ss-e": 0.25}
     m = _metrics([scored, dict.fromkeys(KEYS, NAN), {"ss-q3": 0.25, "ss-h": 0.25, "ss-e": NAN}])
     log.do_eval_epoch_logging(m, "valid-70")
@@ -216,11 +219,11 @@ SS = torch.tensor([[0.5, 0.75, NAN], [NAN, NAN, NAN], [0.25, 0.5, 0.125]])
 
 
 def test_the_report_of_a_single_process():
-    from protein_transformer_amd.losses import _TAIL_FIELDS, _TAIL_KEYS, _TAIL_METRICS, TAIL_LOSSES, LossReport, pack_local, unpack_local
-    assert list(_TAIL_FIELDS) == ["clash", "tm"] and TAIL_LOSSES == ("kabsch",)         # the older registries are what they were
-    assert _TAIL_METRICS == {"ss": KEYS} and list(_TAIL_KEYS) == ["clash", "tm", "kabsch", "ss"]
+    from protein_transformer_amd.losses import REPORT_FIELDS, REPORT_KEYS, LossReport, pack_local, unpack_local
+    assert [f.name for f in REPORT_FIELDS if not f.fixed] == ["clash", "tm", "kabsch", "ss"]      # the tail's order is what it was
+    assert [f.name for f in REPORT_FIELDS if f.fixed] == ["lddt", "slddt", "fape"] and REPORT_KEYS["ss"] == KEYS
     sig = inspect.signature(LossReport.__init__).parameters
-    assert sig["ss"].default is None and sig["with_ss"].default is False
+    assert sig["fields"].default is None and "ss" not in sig          # asked for without a value: fields={"ss": None}
     for channels, tail in (({"lddt": LDDT}, None), ({"lddt": LDDT}, {"clash": CLASH, "tm": TM, "kabsch": KABSCH}), (None, {"tm": TM}),
                            (None, None)):
         plain_buf, plain_layout = pack_local(STATS, MSE, STATUS, RMSD, channels, tail=tail)

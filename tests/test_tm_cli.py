@@ -72,7 +72,9 @@ def test_header_and_rows_without_the_flag_are_byte_identical():
 
 def test_rows_with_the_flag_and_the_epoch_line(capsys):
     from protein_transformer_amd import log
-    assert log._TM == KEYS and log._OPTIONAL[-3:] == KEYS
+    from protein_transformer_amd.eval_metrics import EVAL_METRICS, METRIC_KEYS
+    assert [m.field for m in EVAL_METRICS[:3]] == ["lddt", "clash", "tm"]                # behind lddt and clash, in front of ss
+    assert tuple(k for k, _ in EVAL_METRICS[2].columns) == KEYS and METRIC_KEYS[3:6] == KEYS
     scored = {"tm-ca": 0.75, "gdt-ts": 0.5, "gdt-ha": 0.25}
     # the second batch has no scored protein: NaN, left out of the epoch's mean; the third has
     m = _metrics([scored, dict.fromkeys(KEYS, NAN), {"tm-ca": 0.25, "gdt-ts": 0.25, "gdt-ha": 0.125}])
@@ -109,10 +111,10 @@ TM = torch.tensor([[0.5, 0.75, 0.25], [NAN, NAN, NAN], [0.25, 0.5, 0.125]])
 
 
 def test_the_report_of_a_single_process():
-    from protein_transformer_amd.losses import _TAIL_FIELDS, LossReport, pack_local, unpack_local
-    assert _TAIL_FIELDS["tm"] == KEYS and list(_TAIL_FIELDS) == ["clash", "tm"]
+    from protein_transformer_amd.losses import REPORT_FIELDS, REPORT_KEYS, LossReport, pack_local, unpack_local
+    assert REPORT_KEYS["tm"] == KEYS and [f.name for f in REPORT_FIELDS if not f.fixed][:2] == ["clash", "tm"]
     sig = inspect.signature(LossReport.__init__).parameters
-    assert sig["tm"].default is None and sig["with_tm"].default is False
+    assert sig["fields"].default is None and "tm" not in sig          # asked for without a value: fields={"tm": None}
     for channels, tail in (({"lddt": LDDT}, None), ({"lddt": LDDT}, {"clash": CLASH}), (None, None)):
         plain_buf, plain_layout = pack_local(STATS, MSE, STATUS, RMSD, channels, tail=tail)
         buf, layout = pack_local(STATS, MSE, STATUS, RMSD, channels, tail={**(tail or {}), "tm": TM})
