@@ -273,6 +273,55 @@ size_t ptamd_ss_workspace_bytes(int B, int L);
 int ptamd_ss(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float *score, int32_t *confusion,
              int8_t *states, uint64_t *hbonds, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Side-chain accuracy, for a whole batch (csrc/sidechain.hip): the share of correct rotamers, the mean chi error and the
+ * side-chain RMSD in the residue's own backbone frame - `eval_metrics.sidechain_batch`, `python -m protein_transformer_amd.score`.
+ * The reference has no counterpart.  The chi angles are those of the IUPAC-IUB Commission on Biochemical Nomenclature,
+ * "Abbreviations and symbols for the description of the conformation of polypeptide chains", Biochemistry 9:3471-3479 (1970).
+ * PARITY UNPINNED: what is pinned is this definition, restated in numpy fp64 by tests/sidechain_ref.py.
+ * Inputs as for ptamd_lddt; slots of a residue: 0 N, 1 CA, 2 C, 3 O, 4 + k side-chain atom k in the order of csrc/nerf_tables.h.
+ * Residues whose id is outside 0..19 (PTAMD_PAD_ID, unknown ids) take no part, the rule of ptamd_clash_fwd_bwd.
+ *   Chi angles.  Residue types in the order ACDEFGHIKLMNPQRSTVWY have {0,1,2,3,2,0,2,2,4,2,3,2,2,3,4,1,1,1,2,2} of them.  In
+ *   this atom layout the IUPAC chi_k, k = 1..4, is the dihedral of slots (0,1,4,5), (1,4,5,6), (4,5,6,7), (5,6,7,8) for EVERY
+ *   type: side-chain atom k >= 1 of every type that has a chi_k is built on the parents (N,CA,CB), (CA,CB,atom 1), ... of
+ *   csrc/nerf_tables.h, and the atom names of those slots are the IUPAC ones (ILE: CB, CG1, CD1; THR: OG1; VAL: CG1).  So chi_k
+ *   is also the build torsion of angle column 6 + k.  Dihedral of p0..p3: b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, n1 = b1 x b2,
+ *   n2 = b2 x b3, chi = atan2(|b2| b1 . n2, n1 . n2).
+ *   chi_k of a residue is SCORED when its four TRUE atoms are present (no NaN) and the true |n1|^2 and |n2|^2 both exceed
+ *   1e-8 A^4, a test made in fp64 on the fp32 coordinates, as the frame test of ptamd_fape_fwd_bwd is.  What the prediction
+ *   holds never decides what is scored; its dihedral is taken as it comes.  Delta_k = |chi_pred - chi_true| wrapped into
+ *   [0, 180] degrees; for ASP chi2, GLU chi3, PHE chi2 and TYR chi2, whose far atoms are interchangeable (the pairs of
+ *   ptamd_rename_symmetric), Delta_k = min(Delta_k, 180 - Delta_k).  A hit is Delta_k <= threshold_deg; the usual value is 40.
+ *   The flips of ASN, GLN and HIS (N and O, or the ring, exchanged in the crystallographer's assignment) are NOT resolved.
+ *   Local-frame side-chain RMSD.  A residue is COUNTED when its type has at least one side-chain atom, its true N, CA, C and
+ *   all its true side-chain atoms are present, and its TRUE N, CA, C span a frame: algorithm 21 of Jumper et al. with the 1e-8
+ *   tests of ptamd_fape_fwd_bwd.  In each structure the side-chain atoms are expressed in that structure's own frame,
+ *   x = R^T (p - CA); d2(r) = sum over the atoms of |x_pred - x_true|^2; for ASP, GLU, PHE and TYR the smaller of that sum and
+ *   the same sum with the predicted slots of the pairs of ptamd_rename_symmetric exchanged.
+ *   Unusable prediction.  A non-finite predicted coordinate on any atom of a scored chi or on N, CA, C or a side-chain atom of
+ *   a counted residue, or predicted N, CA, C of a counted residue that span no frame, makes all four scores of that protein NaN
+ *   and its hit counts 0 - the rule of ptamd_ss; its other counts, and every other protein, are what they would be.
+ *   score [B,4] out = {chi1, chi12, chi_mae, sc_rmsd}: chi1 = hits_1 / scored_1; chi12 = among the residues whose chi1 and chi2
+ *   are both scored, the share where both hit; chi_mae = the mean Delta in degrees over every scored chi1..chi4; sc_rmsd =
+ *   sqrt(sum d2(r) / sum atoms) over the counted residues; each NaN when its denominator is 0.
+ *   counts [B,12] out = {scored_1, hit_1, scored_2, hit_2, scored_3, hit_3, scored_4, hit_4, n12, hit12, residues counted,
+ *   atoms counted}.
+ *   per_res [B,L,5] out or NULL = {Delta_1 .. Delta_4 in degrees, sqrt(d2(r) / n_sc)}, NaN where not scored / not counted, and
+ *   on the columns of a residue that its own prediction makes unusable.
+ * Per-residue arithmetic is fp32 on the fp32 inputs (frames: fp64, rounded once), except the two degeneracy tests; prediction
+ * and truth go through the same device functions, so a prediction equal to the truth has Delta == 0 and d2 == 0 exactly.  For
+ * coordinates within +-64 A, bonds of 1-2 A and bond angles of 60-150 degrees a Delta is within 5.5e-4 degrees of its fp64 value
+ * (tests/sidechain_ref.py derives the figure): a Delta that close to the threshold may be decided either way; outside that band
+ * the counts are exact.  Per-protein sums are fp64 in a fixed order, no atomics: two runs give the same bits, and a protein's
+ * result depends neither on the batch around it nor on how far its row is padded.  Workspace: 80 B per 64 residue slots - a
+ * function of (B, L) only.  A NULL pred_crd, true_crd, seq, score or counts, B or L <= 0, L beyond INT_MAX / 28 (the bound of
+ * ptamd_lddt), or a threshold that is negative or not finite: PTAMD_ERR_BAD_SHAPE; workspace NULL or too small:
+ * PTAMD_ERR_WORKSPACE; a workspace that is not 16-byte aligned, or a pred_crd or true_crd that is not 8-byte aligned (the kernel
+ * reads the coordinates as pairs of floats): PTAMD_ERR_ALIGN; nothing is launched or written then.  No state between calls,
+ * nothing read from the environment. */
+size_t ptamd_sidechain_workspace_bytes(int B, int L);
+int ptamd_sidechain(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float threshold_deg,
+                    float *score, int32_t *counts, float *per_res, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
  * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
  * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the

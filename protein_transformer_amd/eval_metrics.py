@@ -21,6 +21,11 @@ TM-score and GDT_TS / GDT_HA (`tm_batch`, `batch_tm`; `train.py --eval_tm`) have
 Secondary-structure agreement (`ss_batch`; `train.py --eval_ss`) has none either: Kabsch & Sander, Biopolymers 22:2577-2637
 (1983), simplified - every hydrogen bond under the energy threshold counts, three states H / E / C - for both structures, and Q3
 between them (csrc/dssp.hip; definition in include/ptamd.h; PARITY UNPINNED).
+
+Side-chain accuracy (`sidechain_batch`, `batch_sidechain`; the scorer `python -m protein_transformer_amd.score`) has none either:
+the IUPAC-IUB (1970) chi1 .. chi4 of both structures, the share within a threshold of the native ones with the ASP / GLU / PHE /
+TYR ambiguity resolved, and the RMSD of the side-chain atoms in each residue's own backbone frame (csrc/sidechain.hip; definition
+in include/ptamd.h; PARITY UNPINNED).  It is not a record of EVAL_METRICS yet: INTEGRATION.md, "Side-chain accuracy".
 """
 from collections import namedtuple
 
@@ -90,6 +95,24 @@ def ss_batch(crd, true_crds, seq, hbonds=False):
                              _lib.ptr(states), _lib.ptr(bits), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "ss")
     return (score, confusion, states, bits) if hbonds else (score, confusion, states)
+
+
+def sidechain_batch(pred_crd, true_crd, seq, threshold=40.0, per_residue=False):
+    """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] -> (score [B,4] = {chi1, chi12,
+    chi_mae, sc_rmsd}, counts [B,12] int32 = {scored, hit of chi1 .. chi4, n12, hit12, residues, atoms}), all on the device, no
+    sync: the side-chain accuracy of csrc/sidechain.hip (definition in include/ptamd.h); `threshold` in degrees.  NaN = nothing in
+    the denominator, or an unusable prediction.  `per_residue`: also per_res [B,L,5] = {Delta_1 .. Delta_4 in degrees, local-frame
+    RMSD of the residue's side chain}, NaN where not scored."""
+    pred_crd, true_crd, seq, B, L = structure_pair(pred_crd, true_crd, seq)
+    dev = seq.device
+    score = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    counts = torch.empty(B, 12, dtype=torch.int32, device=dev)
+    per_res = torch.empty(B, L, 5, dtype=torch.float32, device=dev) if per_residue else None
+    ws = _lib.workspace("sidechain", _lib.lib().ptamd_sidechain_workspace_bytes(B, L), dev)
+    rc = _lib.lib().ptamd_sidechain(_lib.ptr(pred_crd), _lib.ptr(true_crd), _lib.ptr(seq), B, L, float(threshold), _lib.ptr(score),
+                                    _lib.ptr(counts), _lib.ptr(per_res), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "sidechain")
+    return (score, counts, per_res) if per_residue else (score, counts)
 
 
 def clash_batch(crd, seq, tolerance=1.5):
@@ -168,3 +191,11 @@ def batch_tm(pred_sincos, true_crds, input_seqs):
     from .losses import predicted_coords
     crd, _ = predicted_coords(pred_sincos, input_seqs)
     return _finite_means(tm_batch(crd, true_crds, input_seqs)[0])
+
+
+def batch_sidechain(pred_sincos, true_crds, input_seqs, threshold=40.0):
+    """(chi1, chi12, chi_mae, sc_rmsd): means over the proteins with a finite score of the side-chain accuracy of the structures
+    built from pred_sincos (NaN when no protein has one); one host read."""
+    from .losses import predicted_coords
+    crd, _ = predicted_coords(pred_sincos, input_seqs)
+    return _finite_means(sidechain_batch(crd, true_crds, input_seqs, threshold)[0])
