@@ -322,6 +322,45 @@ size_t ptamd_sidechain_workspace_bytes(int B, int L);
 int ptamd_sidechain(const float *pred_crd, const float *true_crd, const int64_t *seq, int B, int L, float threshold_deg,
                     float *score, int32_t *counts, float *per_res, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Superposed per-residue spread of K structures around a reference, for a whole batch (csrc/ensemble.hip): what
+ * `ensemble.predict_ensemble` and `python -m protein_transformer_amd.predict` make of K dropout passes of a model around its
+ * deterministic prediction.  The reference has no counterpart; ptamd_kabsch_rmsd returns one number per pair and ptamd_tm_score
+ * fits by TM-score - this returns what each residue does after a least-squares fit.  There is no truth: every array is a
+ * prediction.  PARITY UNPINNED: what is pinned is this definition, restated in numpy fp64 by tests/ensemble_ref.py.
+ *   ref_crd [B,L*14,3] the reference; sample_crd [B,K,L*14,3] the K samples of every protein; seq [B,L]; slots of a residue:
+ *   0 N, 1 CA, 2 C, 3 O, 4 + k side-chain atom k in the order of csrc/nerf_tables.h.
+ *   Presence.  Residue i is PRESENT when seq[i] is in 0..19 (neither PTAMD_PAD_ID nor an unknown id), the rule of
+ *   ptamd_clash_fwd_bwd; n_b is the number of present residues of protein b.  The ATOMS of a present residue are the slots its
+ *   type has, s < 4 + ptamd_sidechain_atoms(seq[i]); what any other slot holds is never read into a result.
+ *   Usable samples.  Sample (b,k) is USABLE when n_b >= 3 and the C-alpha (slot 1) of every present residue is finite in the
+ *   sample and in the reference.  usable[b] = K', the number of usable samples of protein b.
+ *   Fit.  For a usable sample, (R_k, t_k) is the PROPER rotation (det = +1) and the translation that minimise
+ *   sum_i |R s_ki + t - r_i|^2 over the present C-alphas, s the sample and r the reference: a mirror image is not fitted by a
+ *   reflection.  The moments are fp64 on the fp32 inputs and the solve is that of ptamd_tm_score (csrc/tm_rotation.h: Horn's
+ *   quaternion matrix, cyclic Jacobi); (R_k, t_k) is then rounded to fp32 once.
+ *   rmsd [B,K] out: sqrt((1 / n_b) sum_i |R_k s_ki + t_k - r_i|^2) over the present C-alphas; NaN where the sample is unusable.
+ *   rmsf [B,L,2] out, over the usable samples of the protein:
+ *     [b,i,0] = sqrt((1 / K') sum_k |R_k s_ki + t_k - r_i|^2) on the C-alpha of residue i;
+ *     [b,i,1] = sqrt((1 / K') sum_k (1 / |A_ki|) sum_{a in A_ki} |R_k s_ka + t_k - r_a|^2), A_ki being the atoms of residue i
+ *     that are finite in the reference and in sample k;
+ *     both NaN for an absent residue and where K' = 0.
+ *   A non-finite side-chain (or N, C, O) atom does not make a sample unusable: that atom is LEFT OUT OF ITS OWN TERM, in the sum
+ *   and in |A_ki|; were a residue left with no atom in a usable sample, its all-atom value would be NaN (0 / 0) - which cannot
+ *   happen to a present residue, since its C-alpha is one of its atoms and is finite in every usable sample.
+ * A deviation |R s + t - r|^2 is fp32 on the fp32 inputs under the fp32 (R, t) - the same arithmetic for rmsd and rmsf -, the
+ * sum over the atoms of a residue is fp32 in slot order, the sums over residues and over samples are fp64 in a fixed order, and
+ * every result is rounded to fp32 once.  For coordinates within +-X A every result is within 32 x 2^-23 x X A of its fp64 value
+ * (tests/ensemble_ref.py derives the figure).  No atomics, no order-dependent reduction: two runs give the same bits, and a
+ * protein's result depends neither on the batch around it nor on how far its row is padded.  Every element of rmsd, rmsf and
+ * usable is written, whatever the workspace held on arrival.  Workspace: 64 B per (protein, sample) - the fitted transforms
+ * between the two launches; ptamd_ensemble_workspace_bytes is a function of (B, K, L) only.  A NULL array, B, K or L <= 0,
+ * L beyond INT_MAX / 28 (the bound of ptamd_lddt), or B * K or B * ceil(L / 64) beyond INT_MAX: PTAMD_ERR_BAD_SHAPE (a size of
+ * 0); workspace NULL or too small: PTAMD_ERR_WORKSPACE; a workspace that is not 16-byte aligned: PTAMD_ERR_ALIGN; nothing is
+ * launched or written then.  No state between calls, nothing read from the environment. */
+size_t ptamd_ensemble_workspace_bytes(int B, int K, int L);
+int ptamd_ensemble_spread(const float *ref_crd, const float *sample_crd, const int64_t *seq, int B, int K, int L, float *rmsd,
+                          float *rmsf, int32_t *usable, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
  * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
  * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the

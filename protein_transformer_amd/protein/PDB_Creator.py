@@ -12,6 +12,8 @@ Behaviour kept from the reference:
   * fixed-column record "{:6s}{:5d} {:^4s}{:1s}{:3s} {:1s}{:4d}{:1s}   {:8.3f}{:8.3f}{:8.3f}{:6.2f}{:6.2f}
     {:>2s}{:2s}" with empty chain / altloc / insertion code, occupancy 1, temperature factor 0 and the first letter of
     the atom name as the element symbol (:55-63,84-102);
+  * `b_factors` (not in the reference; `python -m protein_transformer_amd.predict`): one value per residue for the temperature
+    factor of its atoms; without it every line is what it was;
   * header "REMARK  <title>", footer "TER\\nEND          \\n", lines joined by "\\n" (:139-172).
 """
 import numpy as np
@@ -45,7 +47,7 @@ class PDB_Creator(object):
     """Turns an (L * atoms_per_res) x 3 coordinate array plus a sequence (or a residue -> atom-name mapping) into
     PDB text."""
 
-    def __init__(self, coords, seq=None, mapping=None, atoms_per_res=NUM_PREDICTED_COORDS):
+    def __init__(self, coords, seq=None, mapping=None, atoms_per_res=NUM_PREDICTED_COORDS, b_factors=None):
         if hasattr(coords, "detach"):
             coords = coords.detach().cpu().numpy()
         self.coords = np.asarray(coords)
@@ -67,11 +69,15 @@ class PDB_Creator(object):
         self.atoms_per_res = atoms_per_res
         assert self.coords.shape[0] % self.atoms_per_res == 0, \
             f"Coords is not divisible by {atoms_per_res}. {self.coords.shape}"
+        # one temperature factor per RESIDUE, written on each of its atoms (columns 61-66, %6.2f); None: 0.00, as the reference
+        self.b_factors = None if b_factors is None else np.asarray(b_factors, dtype=np.float64).reshape(-1)
+        assert self.b_factors is None or len(self.b_factors) == len(self.mapping), \
+            f"b_factors holds {0 if self.b_factors is None else len(self.b_factors)} values for {len(self.mapping)} residues"
         self.lines = []
 
-    def _atom_line(self, serial, res_nbr, res_name, atom_name, xyz):
+    def _atom_line(self, serial, res_nbr, res_name, atom_name, xyz, b_factor=0):
         return _ATOM_FORMAT.format("ATOM", serial, atom_name, "", ONE_TO_THREE_LETTER_MAP[res_name], "", res_nbr, "",
-                                   xyz[0], xyz[1], xyz[2], 1, 0, atom_name[0], "")
+                                   xyz[0], xyz[1], xyz[2], 1, b_factor, atom_name[0], "")
 
     def _get_lines_for_protein(self):
         self.lines = []
@@ -82,7 +88,8 @@ class PDB_Creator(object):
             for atom_name, xyz in zip(atom_names, res_coords):
                 if atom_name == "PAD" or np.isnan(xyz).sum() > 0 or xyz.sum() == 0:
                     continue
-                self.lines.append(self._atom_line(serial, res_idx + 1, res_name, atom_name, xyz))
+                b = 0 if self.b_factors is None else float(self.b_factors[res_idx])
+                self.lines.append(self._atom_line(serial, res_idx + 1, res_name, atom_name, xyz, b))
                 serial += 1
         return self.lines
 
