@@ -361,6 +361,48 @@ size_t ptamd_ensemble_workspace_bytes(int B, int K, int L);
 int ptamd_ensemble_spread(const float *ref_crd, const float *sample_crd, const int64_t *seq, int B, int K, int L, float *rmsd,
                           float *rmsf, int32_t *usable, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Frame-aligned error matrix of K structures around a reference, for a whole batch (csrc/aligned_error.hip): entry (i, j) is the
+ * error of residue j's C-alpha when the two structures are aligned on the backbone frame of residue i - the aligned error of
+ * Jumper et al., Nature 596:583-589 (2021), supplementary 1.9.7.  ptamd_ensemble_spread fits every sample once, globally, and
+ * smears a hinge over the whole chain; here domains and hinges show as blocks.  With the K dropout samples of
+ * `ensemble.predict_ensemble` it is a self-consistency matrix (`predict --pae`); with K = 1, the native structure as the
+ * reference and the prediction as the sample it is the true aligned error (`score --aligned_error`).  The reference
+ * (protein_transformer) has no counterpart.  PARITY UNPINNED: what is pinned is this definition, restated in numpy fp64 by
+ * tests/aligned_error_ref.py.
+ *   ref_crd [B,L*14,3], sample_crd [B,K,L*14,3], seq [B,L]: the layout of ptamd_ensemble_spread; only slots 0 N, 1 CA, 2 C are
+ *   read.  Residue i is PRESENT when seq[i] is in 0..19, the rule of ptamd_ensemble_spread.
+ *   Frames and points.  Residue i is a FRAME of protein b when it is present, its N, CA and C are finite and within 1e18 in
+ *   ref_crd, and they span a frame (algorithm 21, csrc/backbone_frame.h: |C - CA|^2 and the squared rejection of N - CA from it
+ *   above 1e-8 A^2, tested in fp64 on the fp32 coordinates).  Residue j is a POINT when it is present and its CA is finite and
+ *   within 1e18 in ref_crd.  Frames and points depend on the reference only (the rule of ptamd_fape_fwd_bwd for the truth); n_b
+ *   is the number of points.
+ *   Usable samples.  Sample (b,k) is USABLE when every frame of the reference is a frame in the sample too (finite N, CA, C
+ *   within 1e18 that span a frame) and every point's CA is finite and within 1e18 in the sample.  usable[b] = K', the number of
+ *   usable samples.  What any other slot of a sample holds is never read: a non-finite atom there changes not one bit.
+ *   ae [B,L,L] out: x_ij(S) being the CA of j in the coordinates of frame i of structure S,
+ *     ae[b,i,j] = (1 / K') sum over the usable k of |x_ij(sample k) - x_ij(ref)|,
+ *   the plain Euclidean norm, no epsilon under the root; i = j gives exactly 0.  NaN where i is no frame, where j is no point,
+ *   in padded rows and columns, and everywhere when K' = 0.  Row = frame, column = point: the matrix is not symmetric.
+ *   stats [B,2] out: {mean, tm}.  mean is the mean of the defined entries of protein b.  tm = max over the frames i of
+ *   (1 / n_b) sum_j 1 / (1 + (ae_ij / d0)^2), d0 = 1.24 cbrt(max(n_b, 19) - 15) - 1.8: the pTM formula of the same supplement -
+ *   APPLIED TO THE MEAN ERROR, not to a predicted distribution of errors, so with dropout samples it is a self-consistency
+ *   number and not a calibrated pTM.  Both NaN when no entry is defined.
+ * The frame is fp64 arithmetic on the fp32 coordinates, rounded to fp32 once; x_ij is the one device function for reference and
+ * sample (backbone_frame::local_coords), the difference and the norm are fp32, the sum over k is fp32 in the order k = 0..K-1
+ * followed by one fp32 division; the sums of the stats are fp64 in a fixed order and each stat is rounded to fp32 once.  For
+ * coordinates within +-X A and K <= 8 every entry and the mean are within 72 x 2^-23 x X A of their fp64 values, tm within
+ * 0.65 / d0 times that (tests/aligned_error_ref.py derives the figures).  No atomics, no order-dependent reduction: two runs
+ * give the same bits, and a protein's result depends neither on the batch around it nor on how far its row is padded.  Every
+ * element of ae, stats and usable is written, whatever they and the workspace held on arrival.  Workspace: a 64-byte record per
+ * (protein, structure, residue), the samples' verdicts, and a pair of fp64 partial sums per (row, column tile of 64);
+ * ptamd_aligned_error_workspace_bytes is a function of (B, K, L) only.  A NULL array, B, K or L <= 0, L beyond INT_MAX / 28 (the
+ * bound of ptamd_lddt), or B * (K + 1) beyond INT_MAX or B * ceil(L / 64)^2 beyond INT_MAX / 256 (what one launch addresses):
+ * PTAMD_ERR_BAD_SHAPE (a size of 0); workspace NULL or too small: PTAMD_ERR_WORKSPACE; a workspace that is not 16-byte aligned:
+ * PTAMD_ERR_ALIGN; nothing is launched or written then.  No state between calls, nothing read from the environment. */
+size_t ptamd_aligned_error_workspace_bytes(int B, int K, int L);
+int ptamd_aligned_error(const float *ref_crd, const float *sample_crd, const int64_t *seq, int B, int K, int L, float *ae,
+                        float *stats, int32_t *usable, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Smooth lDDT loss, forward + analytic backward, for a whole batch (csrc/slddt.hip): the training loss `-l slddt`.  The
  * reference has no counterpart; this is the differentiable lDDT of Abramson et al., "Accurate structure prediction of
  * biomolecular interactions with AlphaFold 3", Nature 630:493-500 (2024), supplementary algorithm 27 - sigmoids in place of the

@@ -137,6 +137,8 @@ SIGNATURES = {
     "ptamd_sidechain": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "ptamd_ensemble_workspace_bytes": (_sz, [_i, _i, _i]),
     "ptamd_ensemble_spread": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "ptamd_aligned_error_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ptamd_aligned_error": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "ptamd_slddt_workspace_bytes": (_sz, [_i, _i]),
     "ptamd_slddt_fwd_bwd": (_i, [_p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "ptamd_fape_workspace_bytes": (_sz, [_i, _i]),

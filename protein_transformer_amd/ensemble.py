@@ -6,6 +6,10 @@ RMSF per residue.  `predict_ensemble` makes the samples: one `model.eval()` pass
 `no_grad` - the dropout masks of the encoder, no backward pass - are the ensemble.  The reference (protein_transformer) has no
 counterpart.  `python -m protein_transformer_amd.predict` is the command line on top.
 
+`aligned_error` is the second kernel (csrc/aligned_error.hip): the L x L matrix of how far residue j lies from the reference's
+once a sample and the reference are aligned on the backbone frame of residue i, averaged over the samples.  Like `conf`, the
+matrix and its two summaries (mean, tm) measure the dropout ensemble's SELF-CONSISTENCY and are not calibrated predictions.
+
 `conf` is a dropout SELF-CONSISTENCY score on the lDDT scale: 100 x the mean lDDT-C-alpha of the samples against the reference
 pass.  It is NOT a calibrated pLDDT: how well it tracks the true lDDT has not been measured on any trained model.
 """
@@ -16,7 +20,7 @@ import torch
 from . import _lib
 from .protein.Structure import NUM_PREDICTED_COORDS
 
-Ensemble = namedtuple("Ensemble", "angles crd rmsd rmsf conf usable")
+Ensemble = namedtuple("Ensemble", "angles crd rmsd rmsf conf usable ae ae_stats", defaults=(None, None))
 
 
 def ensemble_spread(ref_crd, sample_crd, seq):
@@ -39,6 +43,32 @@ def ensemble_spread(ref_crd, sample_crd, seq):
                                           _lib.ptr(rmsf), _lib.ptr(usable), _lib.ptr(ws), ws.numel(), _lib.stream())
     _lib.check(rc, "ensemble_spread")
     return rmsd, rmsf, usable
+
+
+def aligned_error(ref_crd, sample_crd, seq):
+    """ref_crd [B, L*14, 3] and sample_crd [B, K, L*14, 3] device tensors, seq [B, L] -> (ae [B,L,L], stats [B,2] = {mean, tm},
+    usable [B] int32), all on the device, no sync: ae[b,i,j] is the mean over the usable samples of how far the C-alpha of
+    residue j lies from the reference's once both are seen from the backbone frame of residue i (csrc/aligned_error.hip;
+    definition in include/ptamd.h).  Row = frame, column = point.  NaN = a residue that is no frame / no point of the reference,
+    padding, or no usable sample."""
+    _lib.require_gpu(ref_crd, sample_crd, seq)
+    B, L = seq.shape
+    assert ref_crd.shape == (B, L * NUM_PREDICTED_COORDS, 3)
+    assert sample_crd.dim() == 4 and sample_crd.shape[0] == B and sample_crd.shape[1] >= 1 and sample_crd.shape[2:] == ref_crd.shape[1:]
+    ref_crd, sample_crd, seq = ref_crd.float().contiguous(), sample_crd.float().contiguous(), seq.contiguous()
+    K = sample_crd.shape[1]
+    dev = seq.device
+    ae = torch.empty(B, L, L, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    usable = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = _lib.workspace("aligned_error", _lib.lib().ptamd_aligned_error_workspace_bytes(B, K, L), dev)
+    rc = _lib.lib().ptamd_aligned_error(_lib.ptr(ref_crd), _lib.ptr(sample_crd), _lib.ptr(seq), B, K, L, _lib.ptr(ae),
+                                        _lib.ptr(stats), _lib.ptr(usable), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "aligned_error")
+    return ae, stats, usable
+
+
+_aligned_error = aligned_error          # (`predict_ensemble` has an argument of that name)
 
 
 def sample_seed(seed, k):
@@ -75,7 +105,7 @@ class _Borrowed:
         return False
 
 
-def predict_ensemble(model, seq, samples=8, seed=0):
+def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False):
     """model: an encoder of this package on the device; seq [B, L] residue ids with trailing padding -> Ensemble(
       angles [B,L,12]   radians, of the deterministic (`model.eval()`) pass;
       crd    [B,L*14,3] its NeRF build (`losses.predicted_coords`): THE prediction - the structure a caller writes;
@@ -83,9 +113,12 @@ def predict_ensemble(model, seq, samples=8, seed=0):
       rmsf   [B,L,2]    per residue over the usable samples, {C-alpha, every atom}  (`ensemble_spread`);
       conf   [B,L]      100 x the mean over the usable samples of the per-residue lDDT-C-alpha (cutoff 15 A, `lddt_batch`) of the
                         sample against `crd`; NaN where that lDDT has no pair or no sample is usable;
-      usable [B]        int32, the number of usable samples).
+      usable [B]        int32, the number of usable samples;
+      ae     [B,L,L]    with `aligned_error=True`: the frame-aligned error matrix of the samples around `crd` (`aligned_error`:
+                        row = frame, column = point), and
+      ae_stats [B,2]    its {mean, tm}; both None otherwise, and then nothing further is launched).
     The K samples are passes in training mode under `no_grad`, pass k under the dropout seed `sample_seed(seed, k)`.  `samples=0`
-    runs the reference pass only: the four ensemble fields are None.  Everything stays on the device; the model is left as it was
+    runs the reference pass only: the ensemble fields are None.  Everything stays on the device; the model is left as it was
     found (`_Borrowed`): a training run that calls this between two steps continues bit-identically."""
     from .eval_metrics import lddt_batch
     from .losses import angles_forward, predicted_coords
@@ -117,4 +150,7 @@ def predict_ensemble(model, seq, samples=8, seed=0):
     lddt_ca = lddt_batch(flat, truth, seq[:, None].expand(B, K, L).reshape(B * K, L))[1][:, :, 1].view(B, K, L)
     ok = torch.isfinite(rmsd)[:, :, None]                        # the usable samples
     conf = 100.0 * torch.where(ok, lddt_ca, torch.zeros_like(lddt_ca)).sum(1) / usable[:, None].float()
-    return Ensemble(angles, crd, rmsd, rmsf, conf, usable)
+    if not aligned_error:
+        return Ensemble(angles, crd, rmsd, rmsf, conf, usable)
+    ae, ae_stats, _ = _aligned_error(crd, sample_crd, seq)
+    return Ensemble(angles, crd, rmsd, rmsf, conf, usable, ae, ae_stats)

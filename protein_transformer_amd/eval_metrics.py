@@ -115,6 +115,18 @@ def sidechain_batch(pred_crd, true_crd, seq, threshold=40.0, per_residue=False):
     return (score, counts, per_res) if per_residue else (score, counts)
 
 
+def aligned_error_batch(pred_crd, true_crd, seq):
+    """pred_crd, true_crd [B, L*14, 3] device tensors (NaN truth = absent atom), seq [B, L] -> (ae [B,L,L], stats [B,2] = {mean,
+    tm}), all on the device, no sync: the TRUE frame-aligned error of csrc/aligned_error.hip (definition in include/ptamd.h) - the
+    truth as the reference, the prediction as its one sample.  ae[b,i,j] = how far the predicted C-alpha of j lies from the true
+    one when both structures are aligned on the backbone frame of i.  NaN = a residue the truth has no frame / no C-alpha for,
+    padding, or a prediction that lacks a frame or a C-alpha the truth has."""
+    from .ensemble import aligned_error
+    pred_crd, true_crd, seq, B, L = structure_pair(pred_crd, true_crd, seq)
+    ae, stats, _ = aligned_error(true_crd, pred_crd.view(B, 1, -1, 3), seq)
+    return ae, stats
+
+
 def clash_batch(crd, seq, tolerance=1.5):
     """crd [B, L*14, 3] predicted coordinates (device), seq [B, L] -> (loss [B], nclash [B] int64, n_atoms [B]), all on the
     device, no sync: the steric clash term of csrc/clash.hip (include/ptamd.h), forward only - Angstrom of overlap per atom

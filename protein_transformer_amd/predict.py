@@ -1,7 +1,7 @@
 """Predict all-atom structures from amino-acid sequences with a trained checkpoint, with a dropout-ensemble confidence.
 
     python -m protein_transformer_amd.predict CHECKPOINT SEQS.fasta --out DIR [--samples 8] [--seed 0] [--batch_residues 16384]
-                                              [--per_residue]
+                                              [--per_residue] [--pae]
 
 reads a checkpoint that `train.checkpoint_model` wrote and a multi-record FASTA file, and for every sequence writes
 `DIR/<identifier>.pdb` - the structure of the deterministic (`model.eval()`) pass, built by the NeRF kernels - and prints one JSON
@@ -9,6 +9,16 @@ line: id, n-res, ens-lddt, ens-rmsd, ens-rmsf-ca, usable, samples.  `--samples K
 masks, no backward pass) make an ensemble around that structure (`ensemble.predict_ensemble`, csrc/ensemble.hip); the temperature
 factor of every atom is its residue's `conf`, and `--per_residue` also writes `DIR/<identifier>.csv`.  The reference
 (protein_transformer) has no counterpart.  One upload and one read back per batch; there is no CPU path.
+
+`--pae` (needs `--samples` >= 1) also writes `DIR/<identifier>.pae.json`, the frame-aligned error matrix of the samples around the
+written structure (`ensemble.aligned_error`, csrc/aligned_error.hip) in the layout of AlphaFold DB's version-2 aligned-error files -
+a list holding one object with `predicted_aligned_error` (n x n, row = the residue whose backbone frame aligns the two structures,
+column = the residue whose C-alpha error is measured, two decimals, `null` where undefined) and `max_predicted_aligned_error` - and
+appends `ens-pae` (its mean) and `ens-ptm` (the pTM formula applied to that mean error) to the JSON line; a protein without a usable
+sample gets no file.  One further read back per batch.
+
+`ens-pae` and `ens-ptm`, like `ens-lddt`, measure the dropout ensemble's SELF-CONSISTENCY: they are NOT calibrated predictions of
+the true aligned error or TM-score, and how well they track them has not been measured on any trained model.
 
 `ens-lddt` (and the temperature factors) is a dropout SELF-CONSISTENCY score on the lDDT scale - 100 x the mean lDDT-C-alpha of the
 samples against the written structure - NOT a calibrated pLDDT: how well it tracks the true lDDT has not been measured on any
@@ -27,6 +37,7 @@ from .protein.PDB_Creator import NUM_PREDICTED_COORDS, PDB_Creator
 from .protein.Sequence import AA_MAP, ONE_TO_THREE_LETTER_MAP, VOCAB
 
 KEYS = ("id", "n-res", "ens-lddt", "ens-rmsd", "ens-rmsf-ca", "usable", "samples")
+PAE_KEYS = ("ens-pae", "ens-ptm")                                 # appended to KEYS by --pae
 PER_RESIDUE_HEADER = ("resnum", "resname", "conf", "rmsf_ca", "rmsf_all")
 
 
@@ -108,9 +119,10 @@ def load_checkpoint(path, device=None):
     return model.to(device)
 
 
-def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None):
+def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None, pae=False):
     """records [(identifier, sequence)] -> per record, in input order, dict(crd [n*14, 3], conf, rmsf_ca, rmsf_all [n], rmsd [K],
-    usable) as host arrays (the ensemble fields None with samples = 0).  One upload and one read back per batch."""
+    usable) as host arrays (the ensemble fields None with samples = 0).  One upload and one read back per batch.  `pae` (needs
+    samples >= 1): also ae [n, n] and ae_stats [2] = {mean, tm}, from one further read back per batch."""
     from .ensemble import predict_ensemble
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     K = int(samples)
@@ -121,11 +133,13 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
         for row, i in enumerate(batch):
             ids[row, :len(records[i][1])] = [AA_MAP[c] for c in records[i][1]]
         seq = torch.from_numpy(ids).to(dev)
-        ens = predict_ensemble(model, seq, samples=K, seed=seed)
+        ens = predict_ensemble(model, seq, samples=K, seed=seed, aligned_error=bool(pae))
         fields = [ens.crd.reshape(B, -1)]
         if K:
             fields += [ens.conf, ens.rmsf.reshape(B, -1), ens.rmsd, ens.usable.float()[:, None]]
         host = torch.cat(fields, dim=1).cpu().numpy()                                    # one read back
+        if pae:
+            matrix = torch.cat([ens.ae.reshape(B, -1), ens.ae_stats], dim=1).cpu().numpy()   # and the one of --pae
         n_crd = L * NUM_PREDICTED_COORDS * 3
         for row, i in enumerate(batch):
             n = len(records[i][1])
@@ -135,6 +149,8 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
                 rmsf = host[row, n_crd + L:n_crd + 3 * L].reshape(L, 2)[:n]
                 r.update(conf=host[row, n_crd:n_crd + n], rmsf_ca=rmsf[:, 0], rmsf_all=rmsf[:, 1],
                          rmsd=host[row, n_crd + 3 * L:n_crd + 3 * L + K], usable=int(host[row, n_crd + 3 * L + K]))
+            if pae:
+                r.update(ae=matrix[row, :L * L].reshape(L, L)[:n, :n], ae_stats=matrix[row, L * L:])
             out[i] = r
     return out
 
@@ -148,6 +164,27 @@ def _finite_mean(x):
 def summary(name, seq, r, samples):
     return {"id": name, "n-res": len(seq), "ens-lddt": _finite_mean(r["conf"]), "ens-rmsd": _finite_mean(r["rmsd"]),
             "ens-rmsf-ca": _finite_mean(r["rmsf_ca"]), "usable": r["usable"], "samples": int(samples)}
+
+
+def pae_summary(r):
+    mean, tm = (float(v) for v in r["ae_stats"])
+    return {"ens-pae": mean if np.isfinite(mean) else None, "ens-ptm": tm if np.isfinite(tm) else None}
+
+
+def pae_document(ae):
+    """ae [n, n] -> what `json.dump` makes an AlphaFold DB version-2 aligned-error file of: a list holding one object, the matrix
+    as a list of rows (row = frame residue, column = point) rounded to two decimals, None (JSON null, never NaN) where an entry
+    is not finite, and the largest entry (None when there is none)."""
+    ae = np.asarray(ae, np.float64)
+    rows = [[round(float(v), 2) if np.isfinite(v) else None for v in row] for row in ae]
+    finite = [v for row in rows for v in row if v is not None]
+    return [{"predicted_aligned_error": rows, "max_predicted_aligned_error": max(finite) if finite else None}]
+
+
+def write_pae(path, ae):
+    with open(path, "w") as f:
+        json.dump(pae_document(ae), f, allow_nan=False, separators=(",", ":"))
+        f.write("\n")
 
 
 def b_factors(r, n):
@@ -175,6 +212,9 @@ def parser():
     ap.add_argument("--batch_residues", type=int, default=16384, help="padded residues per batch (default 16384)")
     ap.add_argument("--per_residue", action="store_true",
                     help="also write <identifier>.csv: residue number, name, conf, C-alpha RMSF and all-atom RMSF")
+    ap.add_argument("--pae", action="store_true",
+                    help="also write <identifier>.pae.json, the frame-aligned error matrix of the samples (AlphaFold DB layout), and "
+                         "add ens-pae and ens-ptm to the JSON line: dropout self-consistency, not calibrated; needs --samples >= 1")
     return ap
 
 
@@ -183,6 +223,8 @@ def main(argv=None):
     try:
         if args.samples < 0 or args.batch_residues < 1:
             raise ValueError("--samples must be >= 0 and --batch_residues >= 1")
+        if args.pae and args.samples < 1:
+            raise ValueError("--pae is made of the dropout samples and needs --samples >= 1")
         records = read_fasta(args.fasta)
         model = load_checkpoint(args.checkpoint)
         for name, seq in records:
@@ -195,12 +237,17 @@ def main(argv=None):
         print(f"predict: {e}", file=sys.stderr)
         return 2
     os.makedirs(args.out, exist_ok=True)
-    results = predict_records(model, records, args.samples, args.seed, args.batch_residues)
+    results = predict_records(model, records, args.samples, args.seed, args.batch_residues, pae=args.pae)
     for (name, seq), r in zip(records, results):
         PDB_Creator(r["crd"], seq=seq, b_factors=b_factors(r, len(seq))).save_pdb(os.path.join(args.out, name + ".pdb"), title=name)
         if args.per_residue:
             write_per_residue(os.path.join(args.out, name + ".csv"), seq, r)
-        print(json.dumps(summary(name, seq, r, args.samples)))
+        line = summary(name, seq, r, args.samples)
+        if args.pae:
+            line.update(pae_summary(r))
+            if r["usable"] > 0:
+                write_pae(os.path.join(args.out, name + ".pae.json"), r["ae"])
+        print(json.dumps(line))
     return 0
 
 

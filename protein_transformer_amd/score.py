@@ -1,11 +1,18 @@
 """Score a model structure against the native one, from two PDB files, with the device metrics of this package.
 
     python -m protein_transformer_amd.score PRED.pdb TRUE.pdb [--threshold 40] [--per_residue OUT.csv]
+                                            [--aligned_error OUT.json]
 
 prints one JSON line: the superposed RMSD, lDDT (all-atom and C-alpha), TM-score and GDT, the secondary-structure agreement, the
 clash term and the side-chain accuracy (chi1 / chi1+2 within `--threshold` degrees, mean chi error, local-frame side-chain RMSD) -
 the kernels behind `train.py --eval_*` and `eval_metrics.sidechain_batch`, on a batch of one.  The reference (protein_transformer)
 has no counterpart.  One upload, one read back; there is no CPU path.
+
+`--aligned_error OUT.json` also writes the TRUE frame-aligned error matrix (`eval_metrics.aligned_error_batch`,
+csrc/aligned_error.hip: TRUE.pdb is the reference, PRED.pdb its one sample) in the layout `predict --pae` writes - row = the residue
+whose backbone frame aligns the two structures, column = the residue whose C-alpha error is measured, `null` in the rows of
+residues the truth has no N, CA, C for and in the columns of residues it has no CA for - and appends `ae-mean` and `ae-tm` to the
+JSON line.  One further read back.
 
 `read_pdb` understands what `protein.PDB_Creator` writes and the ATOM records of an ordinary single-chain PDB entry: the first
 MODEL and the first chain only, no mmCIF.
@@ -23,6 +30,7 @@ from .protein.Sequence import AA_MAP, AA_MAP_INV, ONE_TO_THREE_LETTER_MAP, THREE
 
 KEYS = ("rmsd-full", "lddt-full", "lddt-ca", "tm-ca", "gdt-ts", "gdt-ha", "ss-q3", "ss-h", "ss-e", "clash-full", "sc-chi1", "sc-chi12",
         "sc-chi-mae", "sc-rmsd", "n-res")
+AE_KEYS = ("ae-mean", "ae-tm")                                    # appended to KEYS by --aligned_error
 PER_RESIDUE_HEADER = ("resnum", "resname", "lddt", "chi1_err", "chi2_err", "chi3_err", "chi4_err", "sc_rmsd")
 _SLOT = {one: {name: s for s, name in enumerate(names) if name != "PAD"} for one, names in ATOM_MAP_14.items()}
 
@@ -90,10 +98,11 @@ def _aligned(pred, true):
     return tseq, np.asarray(pcrd, np.float32).reshape(-1, 3), np.asarray(tcrd, np.float32).reshape(-1, 3)
 
 
-def score_structures(pred, true, threshold=40.0, per_residue=False, device=None):
+def score_structures(pred, true, threshold=40.0, per_residue=False, device=None, aligned_error=False):
     """pred, true: each (seq [L], crd [L*14, 3]) as `read_pdb` returns them -> {key of KEYS: float} (n-res: int).  An atom the
     truth lacks is left out of every metric (NaN = absent); an atom only the PREDICTION lacks is a non-finite prediction: the
-    metrics that use it are NaN.  `per_residue`: also an array [L, 6] = {lDDT, chi error 1..4 in degrees, side-chain RMSD}."""
+    metrics that use it are NaN.  `per_residue`: also an array [L, 6] = {lDDT, chi error 1..4 in degrees, side-chain RMSD}.
+    `aligned_error`: the result also has the keys of AE_KEYS, and the matrix [L, L] is returned last (one further read back)."""
     from . import eval_metrics as E
     seq, pcrd, tcrd = _aligned(pred, true)
     L = len(seq)
@@ -114,7 +123,13 @@ def score_structures(pred, true, threshold=40.0, per_residue=False, device=None)
     out = torch.cat([values, rows.reshape(-1)]).cpu().numpy()                            # one read back
     result = {k: float(v) for k, v in zip(KEYS[:-1], out[:len(KEYS) - 1])}
     result["n-res"] = int(L)
-    return (result, out[len(KEYS) - 1:].reshape(L, 6)) if per_residue else result
+    ret = (result, out[len(KEYS) - 1:].reshape(L, 6)) if per_residue else (result,)
+    if aligned_error:
+        ae, stats = E.aligned_error_batch(p, t, s)
+        host = torch.cat([ae.reshape(-1), stats.reshape(-1)]).cpu().numpy()
+        result.update({k: float(v) for k, v in zip(AE_KEYS, host[L * L:])})
+        ret += (host[:L * L].reshape(L, L),)
+    return ret if len(ret) > 1 else result
 
 
 def write_per_residue(path, seq, numbers, rows):
@@ -132,6 +147,9 @@ def parser():
     ap.add_argument("--threshold", type=float, default=40.0, help="degrees within which a chi angle counts as correct (default 40)")
     ap.add_argument("--per_residue", metavar="OUT.csv", default=None,
                     help="also write residue number, name, lDDT, the four chi errors and the side-chain RMSD of every residue")
+    ap.add_argument("--aligned_error", metavar="OUT.json", default=None,
+                    help="also write the true frame-aligned error matrix (the layout of predict --pae; null where the truth lacks "
+                         "the residue) and add ae-mean and ae-tm to the JSON line")
     return ap
 
 
@@ -140,12 +158,16 @@ def main(argv=None):
     try:
         pseq, pcrd = read_pdb(args.pred)
         tseq, tcrd, numbers = read_pdb(args.true, with_numbers=True)
-        result, rows = score_structures((pseq, pcrd), (tseq, tcrd), args.threshold, per_residue=True)
+        result, rows, *matrix = score_structures((pseq, pcrd), (tseq, tcrd), args.threshold, per_residue=True,
+                                                 aligned_error=args.aligned_error is not None)
     except ValueError as e:
         print(f"score: {e}", file=sys.stderr)
         return 2
     if args.per_residue:
         write_per_residue(args.per_residue, tseq, numbers, rows)
+    if args.aligned_error:
+        from .predict import write_pae
+        write_pae(args.aligned_error, matrix[0])
     print(json.dumps(result))
     return 0
 
