@@ -158,7 +158,11 @@ int ptamd_kabsch_rmsd(const float *pred_crd, const float *true_crd, const int64_
  *   for that whole protein (the rule of ptamd_fape_fwd_bwd, found by ptamd_kabsch_rmsd's test on the sums of squares); finite
  *   coordinates of any size are used as they are; the other proteins of the batch are untouched.  Where the two largest
  *   eigenvalues of Horn's 4x4 matrix coincide (for instance n collinear atoms) R is not unique and the loss is not differentiable:
- *   a set of measure zero, on which the call returns the loss and the gradient of one of the minimisers.
+ *   a set of measure zero, on which the call returns the loss - it is the same for every minimiser - and R^T r_k / (n loss_i) under
+ *   ONE of the minimisers: finite, zero outside the present atoms, summing to zero over the atoms and of squared norm 1 / n, as
+ *   under any rotation.  Which minimiser: eigenvalues within Jacobi's rounding of each other (64 eps of the diagonal) count as
+ *   equal and the first column of them is taken (csrc/tm_rotation.h), so the bits are reproducible, and a collinear prediction
+ *   that equals its truth gets R = 1 like any other, not the half turn about the line that ties with it.
  *   Batch.  The reported batch value is the mean over the proteins with a finite loss; the back-propagated quantity is the SUM
  *   over proteins of loss_i, as for every structural loss here.
  *   stats [B,2] out = {loss_i, n_i}; dcrd [B,L*14,3] out, or NULL for the forward-only form (no gradient work; the same bits in

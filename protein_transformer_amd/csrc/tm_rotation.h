@@ -71,11 +71,17 @@ __host__ __device__ inline void solve(const double (&m)[NMOM], int n, double (&x
         }
       }
   }
-  // the column of the largest eigenvalue, picked with selects: no indexed access to the register arrays
+  // the column of the largest eigenvalue, picked with selects: no indexed access to the register arrays.  A later column wins
+  // only by more than Jacobi's own rounding (64 eps of the diagonal): eigenvalues that close are a tie, every column of a tie is
+  // optimal to that rounding, and the FIRST one is taken.  It matters for a set fitted on itself: S is then symmetric to the bit,
+  // row 0 of Horn's matrix is exactly zero and stays so, and column 0 remains the identity quaternion with eigenvalue trace S
+  // untouched.  For collinear atoms (sigma2 = sigma3 = 0) the half turn about the line has that same eigenvalue, and a plain `>`
+  // let the rounding of the sweeps choose between the two: the half turn leaves residuals of 1e-15 where the identity leaves 0.
+  const double tie = 64.0 * 2.220446049250313e-16 * (fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]) + fabs(a[3][3]));
   double ev = a[0][0], qw = v[0][0], qx = v[1][0], qy = v[2][0], qz = v[3][0];
 #pragma unroll
   for (int k = 1; k < 4; ++k) {
-    const bool up = a[k][k] > ev;
+    const bool up = a[k][k] > ev + tie;
     ev = up ? a[k][k] : ev;
     qw = up ? v[0][k] : qw;
     qx = up ? v[1][k] : qx;

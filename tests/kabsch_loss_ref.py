@@ -90,8 +90,9 @@ def horn_rotation(a, b):
                     V[r, p] = c * vrp - s * vrq
                     V[r, q] = s * vrp + c * vrq
     k = 0
-    for j in range(1, 4):                                          # strict: the first of equal eigenvalues
-        if A[j, j] > A[k, k]:
+    tie = 64.0 * 2.220446049250313e-16 * sum(abs(A[i, i]) for i in range(4))
+    for j in range(1, 4):                                          # the first of eigenvalues that are equal to Jacobi's rounding
+        if A[j, j] > A[k, k] + tie:
             k = j
     qw, qx, qy, qz = V[:, k] / np.linalg.norm(V[:, k])
     return np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)],
