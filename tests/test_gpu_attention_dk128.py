@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_attention_fused import _attn_decisions_restated
+from attn_dropout_ref import _attn_decisions_restated
 from test_gpu_attention_plan import _seq, cdiv, delta_floats, device_cus, lengths, ref_lse
 from test_gpu_kernels import assert_close, ref_attention, rnd
 

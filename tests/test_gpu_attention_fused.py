@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_dropout_ref import _attn_decisions_restated
 from test_gpu_kernels import assert_close, ref_attention, rnd
 
 pytestmark = pytest.mark.gpu
@@ -253,38 +254,6 @@ def test_keep_bits_handed_from_forward_to_fused_backward(dev, B, L, H, lens, par
             assert (got == want).all(), f"protein {bb}: {int((got != want).sum())} decisions differ"
         frac = kept[:, :, :, :L].mean()
         assert abs(frac - (1 - p)) < 0.01
-
-
-def _attn_decisions_restated(B, L, H, p, seed, sid):
-    """numpy restatement of csrc/attn_dropout.h (pt_mix32 of common.h on (query, key pair) words, 16-bit halves against a
-    16-bit threshold) in the layout of ptamd_attention_fwd's keep_bits: word [(b, h)][q / 32][key], bit q % 32."""
-    M = np.uint64(0xFFFFFFFF)
-    u = lambda x: (x & M).astype(np.uint64)                          # noqa: E731
-    sh = lambda n: np.uint64(n)                                      # noqa: E731
-
-    def mix32(x):
-        x = u(x)
-        x = u((~x & M) + (x << sh(15)))
-        x = x ^ (x >> sh(12))
-        x = u(x + (x << sh(2)))
-        x = x ^ (x >> sh(4))
-        x = u(x + (x << sh(3)) + (x << sh(11)))
-        return u(x ^ (x >> sh(16)))
-    nt = (L + 31) // 32
-    lk = nt * 32
-    out = np.zeros((B * H, nt, lk), dtype=np.uint32)
-    thr = int(p * 65536.0 + 0.5)
-    idx = np.arange(lk, dtype=np.uint64)
-    for bh in range(B * H):
-        lo = np.uint64((seed & 0xFFFFFFFF) ^ ((bh * 0xC2B2AE35) & 0xFFFFFFFF))
-        hi = np.uint64(((seed >> 32) & 0xFFFFFFFF) ^ ((sid * 0x27D4EB2F) & 0xFFFFFFFF) ^ bh)
-        qp = u(idx * np.uint64(0x9E3779B1) + lo)
-        kp = u((idx >> sh(1)) * np.uint64(0x85EBCA77) + hi)
-        w = mix32(qp[:, None] ^ kp[None, :])                                                    # [q, key]
-        keep = ((w >> (sh(16) * (idx & sh(1)))[None, :]) & np.uint64(0xFFFF)) >= thr
-        for t in range(nt):
-            out[bh, t] = (keep[32 * t:32 * t + 32].astype(np.uint64) << np.arange(32, dtype=np.uint64)[:, None]).sum(0).astype(np.uint32)
-    return out
 
 
 @pytest.mark.parametrize("B,L,H", [(1, 64, 1), (2, 320, 2), (3, 96, 8), (2, 100, 4), (8, 512, 8)])

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_dropout_ref import ref_lse
 from test_gpu_kernels import assert_close, ref_attention, rnd
 
 pytestmark = pytest.mark.gpu
@@ -177,21 +178,10 @@ def _seq(B, L, seed):
     return seq
 
 
-def ref_lse(qkv, key_ok, H):
-    """The kernels' log-sum-exp convention: lse[b, h, q] = ln sum over the protein's keys of exp(q . k / sqrt(dk)) (natural
-    log, scores already scaled; padded queries too), [B, H, L]."""
-    B, L, D3 = qkv.shape
-    D = D3 // 3
-    dk = D // H
-    q, k = (t.reshape(B, L, H, dk).transpose(1, 2) for t in qkv.split(D, dim=-1)[:2])
-    s = (q @ k.transpose(-2, -1) / np.sqrt(dk)).masked_fill(~key_ok[:, None, None, :], -np.inf)
-    return torch.logsumexp(s, dim=-1)
-
-
-@functools.lru_cache(maxsize=None)
-def run_case(dk, B, H, L, kv):
-    """-> (o, lse, dqkv) of the device and their fp64 references; the inputs the suite's f16x2 bars were set on (uniform
-    +-1.5), or for K / V planes the QKV product of ptamd_gemm_hp (Gaussian projections of a similar size)."""
+def case_inputs(dk, B, H, L, kv):
+    """-> (seq, qkv, qkv_in, planes, dout) on the device: the inputs the suite's f16x2 bars were set on (uniform +-1.5), or for
+    K / V planes the QKV product of ptamd_gemm_hp (Gaussian projections of a similar size).  `qkv_in` is what the kernels are
+    given (with planes: NaN in its K | V columns), `qkv` the full product the reference reads."""
     from protein_transformer_amd import kernels as K
     dev = torch.device("cuda:0")
     D, T = H * dk, B * L
@@ -210,6 +200,15 @@ def run_case(dk, B, H, L, kv):
         qkv = rnd((T, 3 * D), 20 + L, 1.5).to(dev)
         qkv_in = qkv
     dout = rnd((T, D), 21 + L).to(dev)
+    return seq, qkv, qkv_in, planes, dout
+
+
+@functools.lru_cache(maxsize=None)
+def run_case(dk, B, H, L, kv):
+    """-> (o, lse, dqkv) of the device and their fp64 references, on `case_inputs`."""
+    from protein_transformer_amd import kernels as K
+    D, T = H * dk, B * L
+    seq, qkv, qkv_in, planes, dout = case_inputs(dk, B, H, L, kv)
     o, lse = K.attention_fwd(qkv_in, seq, H, 0.0, 0, 0, arith=K.GEMM_AUTO, kv=planes)
     dqkv = K.attention_bwd(qkv_in, seq, o, dout, lse, H, 0.0, 0, 0, arith=K.GEMM_AUTO, kv=planes)
     torch.cuda.synchronize()
