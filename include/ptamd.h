@@ -589,6 +589,34 @@ int ptamd_mse_angles_fwd(const float *pred, const float *truth, int64_t T, float
 int ptamd_mse_angles_bwd(const float *pred, const float *truth, int64_t T, const float *sums, float coef,
                          int accumulate, float *dpred, void *stream);
 
+/* Binned-lDDT loss of the confidence head (csrc/plddt.hip; protein_transformer_amd/confidence.py): the pLDDT head of AlphaFold 2
+ * (Jumper et al., Nature 596:583-589 (2021), supplementary 1.9.6) - a softmax over nbins equal bins of [0, 1], trained by
+ * cross-entropy against the bin of the per-residue lDDT-C-alpha of the model's own prediction (ptamd_lddt, per_res[..., 1]).  Not
+ * in the reference.
+ *   logits [T, ld] in, 2 <= nbins <= 64, ld >= nbins a row stride in floats: row t reads logits[t * ld + k] for k < nbins and
+ *     nothing else of the row (the spare columns may hold anything).
+ *   target in, or NULL.  Row t reads target[t * target_stride] (target_stride >= 1: per_res[..., 1] is read in place with 2).
+ *     A row COUNTS when its target is finite; its bin is min(nbins - 1, max(0, (int)floorf(target * nbins))), the product one fp32
+ *     multiply.  NULL is inference: only plddt is written; ce, sums and the workspace may be NULL.
+ *   plddt [T] out, every row: 100 * sum_k p_k (k + 0.5) / nbins, p the max-subtracted softmax of the row's nbins logits.
+ *   ce [T] out: -log p_bin of a counted row, NaN of any other.
+ *   sums [2] out: {mean of ce over the counted rows (NaN when there is none), number of counted rows}.
+ *   ptamd_plddt_bwd: dlogits[t * ldd + k] = coef / sums[1] * (p_k - [k == bin_t]) for k < nbins of a counted row, and exactly 0
+ *     in every other row, in the columns nbins .. ldd - 1 of every row, and everywhere when sums[1] is 0; all T * ldd floats are
+ *     written.  ldd >= nbins; sums is what ptamd_plddt_fwd left, read on the device (no host synchronisation).
+ * fp32 throughout, the sum of ce over the rows in fp64: ptamd_plddt_rows_per_block() rows in index order per workgroup, a record
+ * of 16 bytes each in the workspace (ptamd_plddt_workspace_bytes, a function of T only), then the records in index order in one
+ * further launch.  No atomics: two calls give the same bits.  T <= 0, nbins outside 2 .. 64, ld or ldd below nbins,
+ * target_stride < 1, a NULL array that the call would read or write: PTAMD_ERR_BAD_SHAPE; with a target, a workspace NULL or too
+ * small: PTAMD_ERR_WORKSPACE, not 16-byte aligned: PTAMD_ERR_ALIGN; nothing is launched or written then.  Nothing is allocated,
+ * no state between calls, nothing read from the environment. */
+int ptamd_plddt_rows_per_block(void);
+size_t ptamd_plddt_workspace_bytes(int64_t T);
+int ptamd_plddt_fwd(const float *logits, int ld, const float *target, int target_stride, int64_t T, int nbins, float *plddt,
+                    float *ce, float *sums, void *workspace, size_t workspace_bytes, void *stream);
+int ptamd_plddt_bwd(const float *logits, int ld, const float *target, int target_stride, int64_t T, int nbins, const float *sums,
+                    float coef, float *dlogits, int ldd, void *stream);
+
 /* ------------------------------------------------------------------ encoder building blocks
  * Row-major fp32 GEMM on the matrix cores (the `arith` field selects the arithmetic, see PTAMD_GEMM_* below):
  *     C[M,N] = epilogue( A (*) B )          with reduction length K

@@ -151,6 +151,10 @@ SIGNATURES = {
     "ptamd_mse_angles_workspace_bytes": (_sz, []),
     "ptamd_mse_angles_fwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),
     "ptamd_mse_angles_bwd": (_i, [_p, _p, _i64, _p, _f, _i, _p, _p]),
+    "ptamd_plddt_rows_per_block": (_i, []),
+    "ptamd_plddt_workspace_bytes": (_sz, [_i64]),
+    "ptamd_plddt_fwd": (_i, [_p, _i, _p, _i, _i64, _i, _p, _p, _p, _p, _sz, _p]),
+    "ptamd_plddt_bwd": (_i, [_p, _i, _p, _i, _i64, _i, _p, _f, _p, _i, _p]),
     "ptamd_gemm_workspace_bytes": (_sz, [_i, _i, _i]),
     "ptamd_gate_mask_bytes": (_sz, [_i, _i]),
     "ptamd_gemm": (_i, [C.POINTER(GemmArgs), _p]),

@@ -11,7 +11,8 @@ once a sample and the reference are aligned on the backbone frame of residue i, 
 matrix and its two summaries (mean, tm) measure the dropout ensemble's SELF-CONSISTENCY and are not calibrated predictions.
 
 `conf` is a dropout SELF-CONSISTENCY score on the lDDT scale: 100 x the mean lDDT-C-alpha of the samples against the reference
-pass.  It is NOT a calibrated pLDDT: how well it tracks the true lDDT has not been measured on any trained model.
+pass.  It is NOT a calibrated pLDDT: how well it tracks the true lDDT of a given model is what
+`python -m protein_transformer_amd.confidence calibrate` measures.
 """
 from collections import namedtuple
 
@@ -20,7 +21,7 @@ import torch
 from . import _lib
 from .protein.Structure import NUM_PREDICTED_COORDS
 
-Ensemble = namedtuple("Ensemble", "angles crd rmsd rmsf conf usable ae ae_stats", defaults=(None, None))
+Ensemble = namedtuple("Ensemble", "angles crd rmsd rmsf conf usable ae ae_stats hidden", defaults=(None, None, None))
 
 
 def ensemble_spread(ref_crd, sample_crd, seq):
@@ -90,7 +91,8 @@ class _Borrowed:
 
     def __enter__(self):
         m = self.model
-        self.saved = {k: getattr(m, k) for k in ("training", "dropout_seed", "_step_counter", "auto_guard") if hasattr(m, k)}
+        self.saved = {k: getattr(m, k) for k in ("training", "dropout_seed", "_step_counter", "auto_guard", "keep_hidden")
+                      if hasattr(m, k)}
         guard = self.saved.get("auto_guard")
         if guard is not None:
             m.auto_guard = type(guard)(guard.nlayers, guard.interval, guard.max_slack, guard.max_spread)
@@ -105,7 +107,7 @@ class _Borrowed:
         return False
 
 
-def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False):
+def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False, hidden=False):
     """model: an encoder of this package on the device; seq [B, L] residue ids with trailing padding -> Ensemble(
       angles [B,L,12]   radians, of the deterministic (`model.eval()`) pass;
       crd    [B,L*14,3] its NeRF build (`losses.predicted_coords`): THE prediction - the structure a caller writes;
@@ -116,7 +118,9 @@ def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False):
       usable [B]        int32, the number of usable samples;
       ae     [B,L,L]    with `aligned_error=True`: the frame-aligned error matrix of the samples around `crd` (`aligned_error`:
                         row = frame, column = point), and
-      ae_stats [B,2]    its {mean, tm}; both None otherwise, and then nothing further is launched).
+      ae_stats [B,2]    its {mean, tm}; both None otherwise, and then nothing further is launched;
+      hidden [B*L,d]    with `hidden=True`: the last hidden state of the deterministic pass (`model.keep_hidden`), what the
+                        confidence head reads (confidence.py); None otherwise).
     The K samples are passes in training mode under `no_grad`, pass k under the dropout seed `sample_seed(seed, k)`.  `samples=0`
     runs the reference pass only: the ensemble fields are None.  Everything stays on the device; the model is left as it was
     found (`_Borrowed`): a training run that calls this between two steps continues bit-identically."""
@@ -128,12 +132,15 @@ def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False):
     B, L = seq.shape
     with _Borrowed(model) as m, torch.no_grad():
         m.eval()
+        m.keep_hidden = bool(hidden)             # (for the deterministic pass alone; `_Borrowed` puts the attribute back)
         pred = m(seq)
+        hidden = m.__dict__.pop("last_hidden") if hidden else None
+        m.keep_hidden = False
         seq = seq.to(pred.device, torch.int64).contiguous()
         angles = angles_forward(pred.detach().float().contiguous().view(B, L, -1))
         crd, _ = predicted_coords(pred, seq)
         if K == 0:
-            return Ensemble(angles, crd, None, None, None, None)
+            return Ensemble(angles, crd, None, None, None, None, hidden=hidden)
         m.train()
         sample_crd = torch.empty(B, K, L * NUM_PREDICTED_COORDS, 3, dtype=torch.float32, device=crd.device)
         for k in range(K):
@@ -151,6 +158,6 @@ def predict_ensemble(model, seq, samples=8, seed=0, aligned_error=False):
     ok = torch.isfinite(rmsd)[:, :, None]                        # the usable samples
     conf = 100.0 * torch.where(ok, lddt_ca, torch.zeros_like(lddt_ca)).sum(1) / usable[:, None].float()
     if not aligned_error:
-        return Ensemble(angles, crd, rmsd, rmsf, conf, usable)
+        return Ensemble(angles, crd, rmsd, rmsf, conf, usable, hidden=hidden)
     ae, ae_stats, _ = _aligned_error(crd, sample_crd, seq)
-    return Ensemble(angles, crd, rmsd, rmsf, conf, usable, ae, ae_stats)
+    return Ensemble(angles, crd, rmsd, rmsf, conf, usable, ae, ae_stats, hidden)

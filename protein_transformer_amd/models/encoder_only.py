@@ -336,6 +336,7 @@ class _TransformerBase(nn.Module):
         self.weights_prep = True                     # scales / bounds / planes of the weights in one pass (csrc/wprep.hip), fused into the
                                                      # optimizer step where one precedes the forward pass; False: the separate launches of rounds 2-4
         self.auto_guard = AutoGuard(nlayers)         # measures the slack of the bound-derived f16x2 scales, falls back per site
+        self.keep_hidden = False                     # True: a forward pass leaves its last hidden state [B * L, d] as `last_hidden` (confidence.py)
         self._init_parameters()
 
     # ------------------------------------------------------------------ parameters
@@ -1074,6 +1075,8 @@ class _EncoderFn(torch.autograd.Function):
             saved.append(acts)
         pred = K.linear_fwd(x, W("output_projection.weight"), W("output_projection.bias"),
                             flags=K.EPI_TANH if m.use_tanh_out else 0, arith=ar)
+        if m.keep_hidden:
+            m.last_hidden = x                               # what the output projection read: the input of the confidence head
         if plan.measure_fwd:
             s0 = plan.scales[0]
             s0["guard_stats"][:, 2].zero_()                 # dz1: not measured here (slack 0 = "as good as its bound")

@@ -1,7 +1,7 @@
 """Predict all-atom structures from amino-acid sequences with a trained checkpoint, with a dropout-ensemble confidence.
 
     python -m protein_transformer_amd.predict CHECKPOINT SEQS.fasta --out DIR [--samples 8] [--seed 0] [--batch_residues 16384]
-                                              [--per_residue] [--pae]
+                                              [--per_residue] [--pae] [--plddt]
 
 reads a checkpoint that `train.checkpoint_model` wrote and a multi-record FASTA file, and for every sequence writes
 `DIR/<identifier>.pdb` - the structure of the deterministic (`model.eval()`) pass, built by the NeRF kernels - and prints one JSON
@@ -17,12 +17,17 @@ column = the residue whose C-alpha error is measured, two decimals, `null` where
 appends `ens-pae` (its mean) and `ens-ptm` (the pTM formula applied to that mean error) to the JSON line; a protein without a usable
 sample gets no file.  One further read back per batch.
 
+`--plddt` (needs a checkpoint with a confidence head, written by `python -m protein_transformer_amd.confidence fit`; works with
+`--samples 0`) runs the head on the last hidden state of the deterministic pass - no further pass of the encoder -: the temperature
+factor of every atom is then its residue's pLDDT, `plddt` (the mean over the residues) is appended to the JSON line and
+`--per_residue` gains a last column `plddt`.
+
 `ens-pae` and `ens-ptm`, like `ens-lddt`, measure the dropout ensemble's SELF-CONSISTENCY: they are NOT calibrated predictions of
 the true aligned error or TM-score, and how well they track them has not been measured on any trained model.
 
-`ens-lddt` (and the temperature factors) is a dropout SELF-CONSISTENCY score on the lDDT scale - 100 x the mean lDDT-C-alpha of the
-samples against the written structure - NOT a calibrated pLDDT: how well it tracks the true lDDT has not been measured on any
-trained model.
+`ens-lddt` (and, without `--plddt`, the temperature factors) is a dropout SELF-CONSISTENCY score on the lDDT scale - 100 x the mean
+lDDT-C-alpha of the samples against the written structure - NOT a calibrated pLDDT.  How well it, or the head's `plddt`, tracks the
+true lDDT of a given model is what `python -m protein_transformer_amd.confidence calibrate` measures.
 """
 import argparse
 import csv
@@ -38,7 +43,9 @@ from .protein.Sequence import AA_MAP, ONE_TO_THREE_LETTER_MAP, VOCAB
 
 KEYS = ("id", "n-res", "ens-lddt", "ens-rmsd", "ens-rmsf-ca", "usable", "samples")
 PAE_KEYS = ("ens-pae", "ens-ptm")                                 # appended to KEYS by --pae
+PLDDT_KEYS = ("plddt",)                                           # appended by --plddt, behind PAE_KEYS
 PER_RESIDUE_HEADER = ("resnum", "resname", "conf", "rmsf_ca", "rmsf_all")
+PLDDT_COLUMN = "plddt"                                            # last column of --per_residue under --plddt
 
 
 def read_fasta(path):
@@ -119,10 +126,13 @@ def load_checkpoint(path, device=None):
     return model.to(device)
 
 
-def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None, pae=False):
+def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None, pae=False, head=None):
     """records [(identifier, sequence)] -> per record, in input order, dict(crd [n*14, 3], conf, rmsf_ca, rmsf_all [n], rmsd [K],
     usable) as host arrays (the ensemble fields None with samples = 0).  One upload and one read back per batch.  `pae` (needs
-    samples >= 1): also ae [n, n] and ae_stats [2] = {mean, tm}, from one further read back per batch."""
+    samples >= 1): also ae [n, n] and ae_stats [2] = {mean, tm}, from one further read back per batch.  `head` (a
+    `confidence.ConfidenceHead`): also plddt [n], the head on the last hidden state of the deterministic pass, in the same read
+    back."""
+    from .confidence import mask_padding
     from .ensemble import predict_ensemble
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     K = int(samples)
@@ -133,10 +143,12 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
         for row, i in enumerate(batch):
             ids[row, :len(records[i][1])] = [AA_MAP[c] for c in records[i][1]]
         seq = torch.from_numpy(ids).to(dev)
-        ens = predict_ensemble(model, seq, samples=K, seed=seed, aligned_error=bool(pae))
+        ens = predict_ensemble(model, seq, samples=K, seed=seed, aligned_error=bool(pae), hidden=head is not None)
         fields = [ens.crd.reshape(B, -1)]
         if K:
             fields += [ens.conf, ens.rmsf.reshape(B, -1), ens.rmsd, ens.usable.float()[:, None]]
+        if head is not None:
+            fields.append(mask_padding(head.forward(ens.hidden)[0], seq))                # [B, L], behind everything else
         host = torch.cat(fields, dim=1).cpu().numpy()                                    # one read back
         if pae:
             matrix = torch.cat([ens.ae.reshape(B, -1), ens.ae_stats], dim=1).cpu().numpy()   # and the one of --pae
@@ -149,6 +161,8 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
                 rmsf = host[row, n_crd + L:n_crd + 3 * L].reshape(L, 2)[:n]
                 r.update(conf=host[row, n_crd:n_crd + n], rmsf_ca=rmsf[:, 0], rmsf_all=rmsf[:, 1],
                          rmsd=host[row, n_crd + 3 * L:n_crd + 3 * L + K], usable=int(host[row, n_crd + 3 * L + K]))
+            if head is not None:
+                r.update(plddt=host[row, host.shape[1] - L:host.shape[1] - L + n])
             if pae:
                 r.update(ae=matrix[row, :L * L].reshape(L, L)[:n, :n], ae_stats=matrix[row, L * L:])
             out[i] = r
@@ -188,16 +202,22 @@ def write_pae(path, ae):
 
 
 def b_factors(r, n):
-    """The temperature factor of every residue: its `conf`, 0 where that is NaN or there is no ensemble."""
-    return np.zeros(n) if r["conf"] is None else np.nan_to_num(np.asarray(r["conf"], np.float64), nan=0.0)
+    """The temperature factor of every residue: its `plddt` where a head made one, else its `conf`; 0 where that is NaN or there
+    is neither."""
+    v = r.get("plddt") if r.get("plddt") is not None else r["conf"]
+    return np.zeros(n) if v is None else np.nan_to_num(np.asarray(v, np.float64), nan=0.0)
 
 
 def write_per_residue(path, seq, r):
     nan = np.full(len(seq), np.nan)
     cols = [nan if r[k] is None else r[k] for k in ("conf", "rmsf_ca", "rmsf_all")]
+    header = PER_RESIDUE_HEADER
+    if r.get("plddt") is not None:
+        cols.append(r["plddt"])
+        header += (PLDDT_COLUMN,)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(PER_RESIDUE_HEADER)
+        w.writerow(header)
         for i, c in enumerate(seq):
             w.writerow([i + 1, ONE_TO_THREE_LETTER_MAP[c]] + [f"{col[i]:.4f}" for col in cols])
 
@@ -215,6 +235,9 @@ def parser():
     ap.add_argument("--pae", action="store_true",
                     help="also write <identifier>.pae.json, the frame-aligned error matrix of the samples (AlphaFold DB layout), and "
                          "add ens-pae and ens-ptm to the JSON line: dropout self-consistency, not calibrated; needs --samples >= 1")
+    ap.add_argument("--plddt", action="store_true",
+                    help="run the checkpoint's confidence head (`confidence fit`) on the deterministic pass: temperature factors = "
+                         "pLDDT, `plddt` on the JSON line, a last column `plddt` under --per_residue; works with --samples 0")
     return ap
 
 
@@ -226,6 +249,13 @@ def main(argv=None):
         if args.pae and args.samples < 1:
             raise ValueError("--pae is made of the dropout samples and needs --samples >= 1")
         records = read_fasta(args.fasta)
+        entry = None
+        if args.plddt:                               # (decided on the host, before the model is built)
+            from .confidence import head_from_entry, read_head_entry
+            entry = read_head_entry(args.checkpoint)
+            if entry is None:
+                raise ValueError(f"{args.checkpoint}: --plddt needs a checkpoint with a confidence head, and this one has none "
+                                 "(`python -m protein_transformer_amd.confidence fit` writes one)")
         model = load_checkpoint(args.checkpoint)
         for name, seq in records:
             if len(seq) < 2:
@@ -237,7 +267,8 @@ def main(argv=None):
         print(f"predict: {e}", file=sys.stderr)
         return 2
     os.makedirs(args.out, exist_ok=True)
-    results = predict_records(model, records, args.samples, args.seed, args.batch_residues, pae=args.pae)
+    head = head_from_entry(entry, next(model.parameters()).device) if entry is not None else None
+    results = predict_records(model, records, args.samples, args.seed, args.batch_residues, pae=args.pae, head=head)
     for (name, seq), r in zip(records, results):
         PDB_Creator(r["crd"], seq=seq, b_factors=b_factors(r, len(seq))).save_pdb(os.path.join(args.out, name + ".pdb"), title=name)
         if args.per_residue:
@@ -247,6 +278,8 @@ def main(argv=None):
             line.update(pae_summary(r))
             if r["usable"] > 0:
                 write_pae(os.path.join(args.out, name + ".pae.json"), r["ae"])
+        if args.plddt:
+            line[PLDDT_KEYS[0]] = _finite_mean(r["plddt"])
         print(json.dumps(line))
     return 0
 
