@@ -38,24 +38,29 @@ class GemmArgs(C.Structure):
                 ("gate_mask", _p)]
 
 
+WSCALE_JOB_CAP = 40        # jobs per ptamd_weight_scales launch: MAX_JOBS of csrc/scales.hip
 class WScaleJob(C.Structure):
     _fields_ = [("w", _p), ("rows", _i), ("cols", _i), ("ld", _i), ("row_scale", _p), ("col_scale", _p), ("stats", _p),
                 ("rows_only", _i)]
 
 
+BOUND_JOB_CAP = 40         # jobs per ptamd_bound_scales launch: MAX_JOBS of csrc/scales.hip
 class BoundJob(C.Structure):
     _fields_ = [("ln_gamma_stats", _p), ("ln_beta_stats", _p), ("w_stats", _p), ("w_stat_index", _i), ("bias_stats", _p),
                 ("sqrt_d", _f), ("post_scale", _f), ("out_scale", _p), ("out_value", _p)]
 
 
+LN_REDUCE_JOB_CAP = 16     # sites per ptamd_layernorm_bwd_reduce launch: LN_MAX_REDUCE_JOBS of csrc/elementwise.hip
 class LnReduceJob(C.Structure):
     _fields_ = [("partials", _p), ("D", _i), ("dgamma", _p), ("dbeta", _p)]
 
 
+FILL_JOB_CAP = 8           # tensors per ptamd_fill_u32 launch: MAX_FILLS of csrc/scales.hip
 class FillJob(C.Structure):
     _fields_ = [("dst", _p), ("n", _i64), ("value", _u32)]
 
 
+HP_SPLIT_JOB_CAP = 16      # matrices per ptamd_hp_split_rows / _cols launch: MAX_SPLIT_JOBS of csrc/gemm_hp.hip
 class HpSplitJob(C.Structure):
     _fields_ = [("x", _p), ("ld", _i), ("rows", _i), ("K", _i), ("planes", _p), ("scale", _p)]
 

@@ -6,67 +6,26 @@ current HIP stream through the C ABI.  Everything here requires device tensors; 
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
-from . import _lib
-from ._lib import GemmArgs, GemmHpArgs, check, lib, ptr, stream, workspace
+from ._lib import (BOUND_JOB_CAP, FILL_JOB_CAP, HP_SPLIT_JOB_CAP, LN_REDUCE_JOB_CAP, WSCALE_JOB_CAP, BoundJob, FillJob, GemmArgs,
+                   GemmHpArgs, HpSplitJob, LnReduceJob, WprepBound, WprepPlan, WprepSeg, WScaleJob, check, lib, ptr, stream,
+                   workspace)
 
 EPI_RELU, EPI_TANH, EPI_ACCUM, EPI_GATE, EPI_SLABS = 1, 2, 4, 8, 16
+GEMM_F32, GEMM_BF16X3, GEMM_BF16X3_FULL, GEMM_F16X2, GEMM_AUTO = 0, 1, 2, 3, 4   # ptamd.h: PTAMD_GEMM_*
 
-# bench.py sets this to a list to time every GEMM launch with HIP events recorded on the launch stream:
-# entries are (flops, start_event, end_event).  None (the default) adds no work to the hot path.
+# bench.py sets this to a list to time every GEMM launch with HIP events recorded on the launch stream: entries are
+# (flops, start_event, end_event, matrix-pipe products per fp32 product of the arithmetic the call ran in, which kernel).
+# None (the default) adds no work to the hot path.
 GEMM_TIMING = None
 GEMM_EVENT_POOL = []
 GEMM_BYTES = []          # algorithmic operand bytes (A + B + C [+ residual, + accumulate]) of every timed launch
 GEMM_RESERVED_CUS = 0    # CUs the persistent GEMMs leave free (dp.reserve_cus_for_collectives sets it under data parallelism)
 
 
-def gemm(A, B, C_out, *, M, N, K, lda, ldb, ldc, a_kmajor=False, b_kmajor=False, bias=None, residual=None,
-         ldr=0, flags=0, dropout_p=0.0, seed=0, stream_id=0, split_k=1, colsum=None, gate_scale=0.0, arith=None,
-         a_scale=None, a_scale_stride=1, b_scale=None, b_scale_stride=1, gate_mask=None, ws=None):
-    """C[M,N] = epilogue(A (*) B); operand layouts as documented in ptamd.h.  `arith`: GEMM_* constant of this call
-    (None = the host-side default, `set_gemm_mode`); the library itself keeps no mode.  `ws`: the caller's own workspace
-    (EPI_SLABS: the K slices stay in it; C_out may then be None)."""
-    # split-K slabs and, for the f16x2 arithmetic, the row scales of the two operands
-    if ws is None:
-        ws = workspace("gemm", lib().ptamd_gemm_workspace_bytes(M, N, split_k), A.device)
-    args = GemmArgs(M=M, N=N, K=K, A=A.data_ptr(), lda=lda, a_kmajor=int(a_kmajor), B=B.data_ptr(), ldb=ldb,
-                    b_kmajor=int(b_kmajor), C=C_out.data_ptr() if C_out is not None else ws.data_ptr(), ldc=ldc,
-                    bias=bias.data_ptr() if bias is not None else None,
-                    residual=residual.data_ptr() if residual is not None else None, ldr=ldr, flags=flags,
-                    dropout_p=float(dropout_p), seed=int(seed) & (2 ** 64 - 1), stream_id=int(stream_id),
-                    split_k=int(split_k), workspace=ws.data_ptr() if ws is not None else None,
-                    workspace_bytes=ws.numel() if ws is not None else 0,
-                    colsum=colsum.data_ptr() if colsum is not None else None, gate_scale=float(gate_scale),
-                    arith=int(_DEFAULT_ARITH if arith is None else arith), reserved_cus=int(GEMM_RESERVED_CUS),
-                    a_scale=a_scale.data_ptr() if a_scale is not None else None, a_scale_stride=int(a_scale_stride),
-                    b_scale=b_scale.data_ptr() if b_scale is not None else None, b_scale_stride=int(b_scale_stride),
-                    gate_mask=gate_mask.data_ptr() if gate_mask is not None else None)
-    if GEMM_TIMING is None:
-        check(lib().ptamd_gemm(C.byref(args), stream()), "gemm")
-    else:
-        # events come from a pool created before the timed region: the hot loop only pays two hipEventRecord calls
-        e0, e1 = GEMM_EVENT_POOL.pop(), GEMM_EVENT_POOL.pop()
-        e0.record()
-        check(lib().ptamd_gemm(C.byref(args), stream()), "gemm")
-        e1.record()
-        # (flops, events, matrix-pipe products per fp32 product of the arithmetic this call ran in)
-        # (flops, events, matrix-pipe products per fp32 product of the arithmetic this call ran in, which kernel)
-        nprod = lib().ptamd_gemm_products(C.byref(args))
-        kind = "dW" if (a_kmajor and b_kmajor) else ("dX" if b_kmajor else "fwd")
-        GEMM_TIMING.append((2.0 * M * N * K, e0, e1, nprod,
-                            f"ptamd_gemm {kind} (staging kernel, A_KMAJOR={int(bool(a_kmajor))} B_KMAJOR={int(bool(b_kmajor))} NPROD={nprod})"))
-        GEMM_BYTES.append(4 * (M * K + N * K + M * N * (1 + (residual is not None) + bool(flags & EPI_ACCUM))))
-    return C_out
-
-
-GEMM_F32, GEMM_BF16X3, GEMM_BF16X3_FULL, GEMM_F16X2, GEMM_AUTO = 0, 1, 2, 3, 4   # ptamd.h: PTAMD_GEMM_*
-
-
-
-
 def _env_arith():
-    import os
     try:
         v = int(os.environ.get("PTAMD_GEMM_MODE", GEMM_AUTO))
     except ValueError:
@@ -90,6 +49,76 @@ def set_gemm_mode(mode):
 
 def get_gemm_mode():
     return _DEFAULT_ARITH
+
+
+def _arith(arith):
+    """The arithmetic of a call: its own, or the host-side default."""
+    return int(_DEFAULT_ARITH if arith is None else arith)
+
+
+def _addr(t):
+    """Device address of an optional tensor as a struct field (None -> NULL; `ptr` is the same for positional arguments)."""
+    return None if t is None else t.data_ptr()
+
+
+def _launch_gemm(fn, what, args, record):
+    """One launch of the GEMM family: fn(*args, stream).  While bench.py times (GEMM_TIMING is a list) the launch sits between
+    two events of the pool - created before the timed region: the hot loop only pays two hipEventRecord calls - and
+    `record()` -> (flops, nprod, label, operand bytes) is evaluated; otherwise it is never called."""
+    if GEMM_TIMING is None:
+        check(fn(*args, stream()), what)
+        return
+    e0, e1 = GEMM_EVENT_POOL.pop(), GEMM_EVENT_POOL.pop()
+    e0.record()
+    check(fn(*args, stream()), what)
+    e1.record()
+    flops, nprod, label, nbytes = record()
+    GEMM_TIMING.append((flops, e0, e1, nprod, label))
+    GEMM_BYTES.append(nbytes)
+
+
+def _launch_jobs(struct, cap, fn, what, jobs):
+    """fn(array of `struct`, count, stream) on `jobs` (an iterable of `struct`), at most `cap` of them per launch."""
+    jobs = list(jobs)
+    for i in range(0, len(jobs), cap):
+        chunk = jobs[i:i + cap]
+        check(fn((struct * len(chunk))(*chunk), len(chunk), stream()), what)
+
+
+def _gemm_args(M, N, K, A, lda, a_kmajor, B, ldb, b_kmajor, C_out, ldc, flags, split_k, ws, colsum, arith, a_scale,
+               a_scale_stride, b_scale, b_scale_stride, bias=None, residual=None, ldr=0, dropout_p=0.0, seed=0, stream_id=0,
+               gate_scale=0.0, gate_mask=None):
+    """The argument block of ptamd_gemm / of one member of ptamd_gemm_group (C_out None: the slabs stay in `ws`)."""
+    return GemmArgs(M=M, N=N, K=K, A=A.data_ptr(), lda=lda, a_kmajor=int(a_kmajor), B=B.data_ptr(), ldb=ldb,
+                    b_kmajor=int(b_kmajor), C=(ws if C_out is None else C_out).data_ptr(), ldc=ldc, bias=_addr(bias),
+                    residual=_addr(residual), ldr=ldr, flags=flags, dropout_p=float(dropout_p), seed=int(seed) & (2 ** 64 - 1),
+                    stream_id=int(stream_id), split_k=int(split_k), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                    colsum=_addr(colsum), gate_scale=float(gate_scale), arith=arith, reserved_cus=int(GEMM_RESERVED_CUS),
+                    a_scale=_addr(a_scale), a_scale_stride=int(a_scale_stride), b_scale=_addr(b_scale),
+                    b_scale_stride=int(b_scale_stride), gate_mask=_addr(gate_mask))
+
+
+def gemm(A, B, C_out, *, M, N, K, lda, ldb, ldc, a_kmajor=False, b_kmajor=False, bias=None, residual=None,
+         ldr=0, flags=0, dropout_p=0.0, seed=0, stream_id=0, split_k=1, colsum=None, gate_scale=0.0, arith=None,
+         a_scale=None, a_scale_stride=1, b_scale=None, b_scale_stride=1, gate_mask=None, ws=None):
+    """C[M,N] = epilogue(A (*) B); operand layouts as documented in ptamd.h.  `arith`: GEMM_* constant of this call
+    (None = the host-side default, `set_gemm_mode`); the library itself keeps no mode.  `ws`: the caller's own workspace
+    (EPI_SLABS: the K slices stay in it; C_out may then be None)."""
+    # split-K slabs and, for the f16x2 arithmetic, the row scales of the two operands
+    if ws is None:
+        ws = workspace("gemm", lib().ptamd_gemm_workspace_bytes(M, N, split_k), A.device)
+    args = _gemm_args(M, N, K, A, lda, a_kmajor, B, ldb, b_kmajor, C_out, ldc, flags, split_k, ws, colsum, _arith(arith),
+                      a_scale, a_scale_stride, b_scale, b_scale_stride, bias, residual, ldr, dropout_p, seed, stream_id,
+                      gate_scale, gate_mask)
+
+    def record():
+        nprod = lib().ptamd_gemm_products(C.byref(args))
+        kind = "dW" if (a_kmajor and b_kmajor) else ("dX" if b_kmajor else "fwd")
+        return (2.0 * M * N * K, nprod,
+                f"ptamd_gemm {kind} (staging kernel, A_KMAJOR={int(bool(a_kmajor))} B_KMAJOR={int(bool(b_kmajor))} NPROD={nprod})",
+                4 * (M * K + N * K + M * N * (1 + (residual is not None) + bool(flags & EPI_ACCUM))))
+    _launch_gemm(lib().ptamd_gemm, "gemm", (C.byref(args),), record)
+    return C_out
 
 
 class HpOperand:
@@ -124,27 +153,17 @@ def gemm_hp(a, b, C_out, *, bias=None, residual=None, ldr=0, flags=0, dropout_p=
     assert a.K == b.K
     M, N = a.rows, b.rows
     ws = workspace("gemm_hp", lib().ptamd_gemm_hp_workspace_bytes(M, N, split_k), C_out.device) if split_k > 1 else None
+    kv_planes, kv_inv = kv if kv is not None else (None, None)
     args = GemmHpArgs(M=M, N=N, K=a.K, A=a.planes.data_ptr(), A_scale=a.scale.data_ptr(), B=b.planes.data_ptr(),
-                      B_scale=b.scale.data_ptr(), C=C_out.data_ptr(), ldc=C_out.stride(0),
-                      bias=bias.data_ptr() if bias is not None else None,
-                      residual=residual.data_ptr() if residual is not None else None, ldr=ldr, flags=flags,
-                      dropout_p=float(dropout_p), seed=int(seed) & (2 ** 64 - 1), stream_id=int(stream_id),
-                      split_k=int(split_k), workspace=ws.data_ptr() if ws is not None else None,
+                      B_scale=b.scale.data_ptr(), C=C_out.data_ptr(), ldc=C_out.stride(0), bias=_addr(bias),
+                      residual=_addr(residual), ldr=ldr, flags=flags, dropout_p=float(dropout_p),
+                      seed=int(seed) & (2 ** 64 - 1), stream_id=int(stream_id), split_k=int(split_k), workspace=_addr(ws),
                       workspace_bytes=ws.numel() if ws is not None else 0, gate_scale=float(gate_scale),
-                      reserved_cus=int(GEMM_RESERVED_CUS),
-                      gate_mask=gate_mask.data_ptr() if gate_mask is not None else None,
-                      gate_mask_out=gate_mask_out.data_ptr() if gate_mask_out is not None else None,
-                      kv_planes=kv[0].data_ptr() if kv is not None else None, kv_inv=kv[1].data_ptr() if kv is not None else None,
-                      kv_col0=int(kv_col0), kv_heads=int(kv_heads))
-    if GEMM_TIMING is None:
-        check(lib().ptamd_gemm_hp(C.byref(args), stream()), "gemm_hp")
-    else:
-        e0, e1 = GEMM_EVENT_POOL.pop(), GEMM_EVENT_POOL.pop()
-        e0.record()
-        check(lib().ptamd_gemm_hp(C.byref(args), stream()), "gemm_hp")
-        e1.record()
-        GEMM_TIMING.append((2.0 * M * N * a.K, e0, e1, 3, "ptamd_gemm_hp (LDS-DMA kernel gemm_hp3_kernel, NPROD=3)"))
-        GEMM_BYTES.append(4 * (M * a.K + N * a.K + M * N * (1 + (residual is not None) + bool(flags & EPI_ACCUM))))
+                      reserved_cus=int(GEMM_RESERVED_CUS), gate_mask=_addr(gate_mask), gate_mask_out=_addr(gate_mask_out),
+                      kv_planes=_addr(kv_planes), kv_inv=_addr(kv_inv), kv_col0=int(kv_col0), kv_heads=int(kv_heads))
+    _launch_gemm(lib().ptamd_gemm_hp, "gemm_hp", (C.byref(args),), lambda: (
+        2.0 * M * N * a.K, 3, "ptamd_gemm_hp (LDS-DMA kernel gemm_hp3_kernel, NPROD=3)",
+        4 * (M * a.K + N * a.K + M * N * (1 + (residual is not None) + bool(flags & EPI_ACCUM)))))
     return C_out
 
 
@@ -175,27 +194,28 @@ def pick_split_k_rows(M, N, K, slots=256):
     return max(1, min(K // 512, slots // tiles))
 
 
-def linear_fwd(x, w, b, out=None, defer_reduce=False, **epi):
-    """y[T,N] = x[T,K] w[N,K]^T + b with a fused epilogue.  `defer_reduce` (the caller hands the result to layernorm_fwd
-    and nothing else): where the product is split over K (few tokens) and its epilogue is bias + dropout + residual, the K
-    slices stay unreduced and a `PendingRows` is returned - that LayerNorm makes the rows as it reads them (same bits)."""
+def linear_fwd(x, w, b, out=None, defer_reduce=False, *, residual=None, ldr=0, flags=0, dropout_p=0.0, seed=0, stream_id=0,
+               arith=None, **rest):
+    """y[T,N] = x[T,K] w[N,K]^T + b with a fused epilogue (`rest`: further operands of `gemm`).  `defer_reduce` (the caller
+    hands the result to layernorm_fwd and nothing else): where the product is split over K (few tokens) and its epilogue is
+    bias + dropout + residual, the K slices stay unreduced and a `PendingRows` is returned - that LayerNorm makes the rows
+    as it reads them (same bits)."""
     T, K = x.shape
     N = w.shape[0]
     sk = pick_split_k_rows(T, N, K)
-    if defer_reduce and DEFER_REDUCE and sk > 1 and out is None and b is not None and N % 4 == 0 and N <= 512 and \
-            epi.get("flags", 0) == 0 and epi.get("residual") is not None and epi.get("ldr") == N and \
-            epi["residual"].is_contiguous() and int(_DEFAULT_ARITH if epi.get("arith") is None else epi["arith"]) != GEMM_F32:
-        n = effective_splits(K, sk)
-        if 2 <= n <= 4:
+    if defer_reduce and out is None and b is not None and flags == 0 and residual is not None and ldr == N and \
+            residual.is_contiguous():
+        n = deferred_slabs(N, K, sk, arith)
+        if n:
             ws = workspace("gemm_slabs", lib().ptamd_gemm_workspace_bytes(T, N, sk), x.device)
-            rest = {k: v for k, v in epi.items() if k not in ("residual", "ldr", "dropout_p", "seed", "stream_id", "flags")}
-            gemm(x, w, None, M=T, N=N, K=K, lda=x.stride(0), ldb=w.stride(0), ldc=N, split_k=sk, flags=EPI_SLABS, ws=ws, **rest)
-            return PendingRows(Slabs(ws, n, T * N, (T, N)), b, epi["residual"], epi.get("dropout_p", 0.0), epi.get("seed", 0),
-                               epi.get("stream_id", 0))
+            gemm(x, w, None, M=T, N=N, K=K, lda=x.stride(0), ldb=w.stride(0), ldc=N, split_k=sk, flags=EPI_SLABS, arith=arith,
+                 ws=ws, **rest)
+            return PendingRows(Slabs(ws, n, T * N, (T, N)), b, residual, dropout_p, seed, stream_id)
     if out is None:
         out = torch.empty(T, N, dtype=torch.float32, device=x.device)
-    return gemm(x, w, out, M=T, N=N, K=K, lda=x.stride(0), ldb=w.stride(0), ldc=out.stride(0), bias=b,
-                split_k=sk, **epi)
+    return gemm(x, w, out, M=T, N=N, K=K, lda=x.stride(0), ldb=w.stride(0), ldc=out.stride(0), bias=b, split_k=sk,
+                residual=residual, ldr=ldr, flags=flags, dropout_p=dropout_p, seed=seed, stream_id=stream_id, arith=arith,
+                **rest)
 
 
 def gate_mask_buffer(M, N, device):
@@ -252,6 +272,17 @@ def effective_splits(K, split_k):
     return -(-K // per)
 
 
+def deferred_slabs(cols, red, split_k, arith):
+    """How many K slices a product with `cols` output columns and a reduction of length `red`, asked to split `split_k` ways,
+    may leave unreduced for a LayerNorm kernel to sum, or 0 if it has to reduce them itself.  The limits are those of
+    ptamd_layernorm_fwd_sum / ptamd_layernorm_bwd_dropout (float4 rows of at most 512 columns, 2 ... 4 slabs); the f32
+    arithmetic keeps its own reduction.  (The output rows do not enter: they only decide `split_k`, pick_split_k_rows.)"""
+    if not DEFER_REDUCE or split_k <= 1 or cols % 4 or cols > 512 or _arith(arith) == GEMM_F32:
+        return 0
+    n = effective_splits(red, split_k)
+    return n if 2 <= n <= 4 else 0
+
+
 def linear_bwd_input(dy, w, out=None, flags=0, gate=None, gate_dropout_p=0.0, arith=None, gate_mask=None, defer_reduce=False,
                      **scales):
     """dx[T,K] = dy[T,N] w[N,K];  with `gate` (the saved output of a ReLU + dropout layer, [T,K]) the product is passed
@@ -262,10 +293,9 @@ def linear_bwd_input(dy, w, out=None, flags=0, gate=None, gate_dropout_p=0.0, ar
     T, N = dy.shape
     K = w.shape[1]
     sk = pick_split_k_rows(T, K, N)
-    if defer_reduce and DEFER_REDUCE and sk > 1 and out is None and gate is None and gate_mask is None and flags == 0 and \
-            K % 4 == 0 and K <= 512 and int(_DEFAULT_ARITH if arith is None else arith) != GEMM_F32:
-        n = effective_splits(N, sk)
-        if 2 <= n <= 4:
+    if defer_reduce and out is None and gate is None and gate_mask is None and flags == 0:
+        n = deferred_slabs(K, N, sk, arith)
+        if n:
             # the slabs' own workspace (the shared one is the next product's); the kernel that sums them is enqueued on
             # this stream before the next product of this kind writes it
             ws = workspace("gemm_slabs", lib().ptamd_gemm_workspace_bytes(T, K, sk), dy.device)
@@ -275,7 +305,7 @@ def linear_bwd_input(dy, w, out=None, flags=0, gate=None, gate_dropout_p=0.0, ar
     if out is None:
         out = torch.empty(T, K, dtype=torch.float32, device=dy.device)
     if gate_mask is not None and sk == 1 and K % 4 == 0 and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0 and \
-            int(_DEFAULT_ARITH if arith is None else arith) in (GEMM_F16X2, GEMM_AUTO) and N >= 32 and \
+            _arith(arith) in (GEMM_F16X2, GEMM_AUTO) and N >= 32 and \
             dy.shape[0] * dy.stride(0) * 4 < 2 ** 32 and w.shape[0] * w.stride(0) * 4 < 2 ** 32:   # (else ptamd_gemm runs in f32)
         return gemm(dy, w, out, M=T, N=K, K=N, lda=dy.stride(0), ldb=w.stride(0), ldc=out.stride(0), b_kmajor=True, split_k=1,
                     flags=flags | EPI_GATE, gate_mask=gate_mask, gate_scale=1.0 / (1.0 - gate_dropout_p), arith=arith, **scales)
@@ -328,29 +358,16 @@ def linear_bwd_weight_group(jobs, split_k):
     products, one for all their split-K reductions (ptamd_gemm_group; every job f16x2 with uniform scales).  Bit for bit
     what the separate calls give with the same `split_k`."""
     arr = (GemmArgs * len(jobs))()
-    flops = 0.0
-    nbytes = 0
     for j, (dy, x, dw, dbias, dy_scale, x_scale) in enumerate(jobs):
         T, N = dy.shape
         Kd = x.shape[1]
         ws = workspace(f"gemm_group{j}", lib().ptamd_gemm_workspace_bytes(N, Kd, split_k), dw.device)
-        arr[j] = GemmArgs(M=N, N=Kd, K=T, A=dy.data_ptr(), lda=dy.stride(0), a_kmajor=1, B=x.data_ptr(), ldb=x.stride(0),
-                          b_kmajor=1, C=dw.data_ptr(), ldc=dw.stride(0), bias=None, residual=None, ldr=0, flags=EPI_ACCUM,
-                          dropout_p=0.0, seed=0, stream_id=0, split_k=int(split_k), workspace=ws.data_ptr(),
-                          workspace_bytes=ws.numel(), colsum=dbias.data_ptr() if dbias is not None else None, gate_scale=0.0,
-                          arith=GEMM_F16X2, reserved_cus=int(GEMM_RESERVED_CUS), a_scale=dy_scale.data_ptr(), a_scale_stride=0,
-                          b_scale=x_scale.data_ptr(), b_scale_stride=0)
-        flops += 2.0 * N * Kd * T
-        nbytes += 4 * (N * T + Kd * T + 2 * N * Kd)
-    if GEMM_TIMING is None:
-        check(lib().ptamd_gemm_group(arr, len(jobs), stream()), "gemm_group")
-    else:
-        e0, e1 = GEMM_EVENT_POOL.pop(), GEMM_EVENT_POOL.pop()
-        e0.record()
-        check(lib().ptamd_gemm_group(arr, len(jobs), stream()), "gemm_group")
-        e1.record()
-        GEMM_TIMING.append((flops, e0, e1, 3, "ptamd_gemm_group dW (staging kernel on a group + one split-K reduce, NPROD=3)"))
-        GEMM_BYTES.append(nbytes)
+        arr[j] = _gemm_args(N, Kd, T, dy, dy.stride(0), 1, x, x.stride(0), 1, dw, dw.stride(0), EPI_ACCUM, split_k, ws, dbias,
+                            GEMM_F16X2, dy_scale, 0, x_scale, 0)
+    _launch_gemm(lib().ptamd_gemm_group, "gemm_group", (arr, len(jobs)), lambda: (
+        sum(2.0 * a.M * a.N * a.K for a in arr), 3,
+        "ptamd_gemm_group dW (staging kernel on a group + one split-K reduce, NPROD=3)",
+        sum(4 * (a.M * a.K + a.N * a.K + 2 * a.M * a.N) for a in arr)))
 
 
 def colsum(x, out, accumulate=True):
@@ -392,49 +409,44 @@ def hp_view(planes, scale, rows, K):
 
 def hp_split_rows(mats, outs):
     """K-contiguous matrices -> HpOperands `outs` (allocated by the caller) in one launch per 16 matrices."""
-    from ._lib import HpSplitJob
-    for i in range(0, len(mats), 16):
-        chunk = list(zip(mats[i:i + 16], outs[i:i + 16]))
-        arr = (HpSplitJob * len(chunk))()
-        for k, (w, o) in enumerate(chunk):
-            assert w.dim() == 2 and w.stride(1) == 1 and (o.rows, o.K) == tuple(w.shape)
-            # (the kernel writes ptamd_hp_padded_rows(rows) scales: the view must own the padding rows' entries too)
-            assert o.scale.numel() >= lib().ptamd_hp_padded_rows(o.rows), "hp_split_rows: no room for the padding rows' scales"
-            arr[k] = HpSplitJob(x=w.data_ptr(), ld=w.stride(0), rows=w.shape[0], K=w.shape[1], planes=o.planes.data_ptr(),
-                                scale=o.scale.data_ptr())
-        check(lib().ptamd_hp_split_rows(arr, len(chunk), stream()), "hp_split_rows")
+    def job(w, o):
+        assert w.dim() == 2 and w.stride(1) == 1 and (o.rows, o.K) == tuple(w.shape)
+        # (the kernel writes ptamd_hp_padded_rows(rows) scales: the view must own the padding rows' entries too)
+        assert o.scale.numel() >= lib().ptamd_hp_padded_rows(o.rows), "hp_split_rows: no room for the padding rows' scales"
+        return HpSplitJob(x=w.data_ptr(), ld=w.stride(0), rows=w.shape[0], K=w.shape[1], planes=o.planes.data_ptr(),
+                          scale=o.scale.data_ptr())
+    _launch_jobs(HpSplitJob, HP_SPLIT_JOB_CAP, lib().ptamd_hp_split_rows, "hp_split_rows", map(job, mats, outs))
     return outs
 
 
 def hp_split_cols(mats, scales, outs):
     """Row-contiguous matrices [K, rows] -> HpOperands of their transposes (rows x K) with GIVEN row scales (int32 / float32
     tensors holding powers of two, e.g. the column scales of ptamd_weight_scales) in one launch per 16 matrices."""
-    from ._lib import HpSplitJob
-    for i in range(0, len(mats), 16):
-        chunk = list(zip(mats[i:i + 16], scales[i:i + 16], outs[i:i + 16]))
-        arr = (HpSplitJob * len(chunk))()
-        for k, (w, sc, o) in enumerate(chunk):
-            assert w.dim() == 2 and w.stride(1) == 1 and (o.rows, o.K) == (w.shape[1], w.shape[0]) and sc.numel() >= o.rows
-            arr[k] = HpSplitJob(x=w.data_ptr(), ld=w.stride(0), rows=o.rows, K=o.K, planes=o.planes.data_ptr(), scale=sc.data_ptr())
-        check(lib().ptamd_hp_split_cols(arr, len(chunk), stream()), "hp_split_cols")
+    def job(w, sc, o):
+        assert w.dim() == 2 and w.stride(1) == 1 and (o.rows, o.K) == (w.shape[1], w.shape[0]) and sc.numel() >= o.rows
+        return HpSplitJob(x=w.data_ptr(), ld=w.stride(0), rows=o.rows, K=o.K, planes=o.planes.data_ptr(), scale=sc.data_ptr())
+    _launch_jobs(HpSplitJob, HP_SPLIT_JOB_CAP, lib().ptamd_hp_split_cols, "hp_split_cols", map(job, mats, scales, outs))
     return outs
 
 
-def _ln_workspace(D, device, pending):
-    """Workspace of one LayerNorm backward; with a `pending` list (deferred reduction) every pending site gets its own."""
-    tag = "ln" if pending is None else f"ln{len(pending)}"
-    return workspace(tag, lib().ptamd_layernorm_bwd_workspace_bytes(D), device)
+def _ln_bwd_site(launch, D, device, dgamma, dbeta, pending):
+    """One LayerNorm backward launch(dgamma, dbeta, workspace, its bytes).  With a `pending` list the (dgamma, dbeta)
+    reduction of this site is left to `layernorm_bwd_flush` (the kernel gets NULL for both, every pending site its own
+    workspace, and a full list is flushed first); without one the kernel finishes it."""
+    if pending is not None and len(pending) >= LN_REDUCE_JOB_CAP:
+        layernorm_bwd_flush(pending)
+    ws = workspace("ln" if pending is None else f"ln{len(pending)}", lib().ptamd_layernorm_bwd_workspace_bytes(D), device)
+    if pending is None:
+        launch(ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel())
+    else:
+        launch(None, None, ptr(ws), ws.numel())
+        pending.append((ws, D, dgamma, dbeta))
 
 
 def layernorm_bwd_flush(pending):
     """Finish the deferred (dgamma, dbeta) reductions in `pending` with one launch per 16 sites; empties the list."""
-    from ._lib import LnReduceJob
-    for i in range(0, len(pending), 16):
-        chunk = pending[i:i + 16]
-        arr = (LnReduceJob * len(chunk))()
-        for k, (ws, D, dg, db) in enumerate(chunk):
-            arr[k] = LnReduceJob(partials=ws.data_ptr(), D=D, dgamma=dg.data_ptr(), dbeta=db.data_ptr())
-        check(lib().ptamd_layernorm_bwd_reduce(arr, len(chunk), stream()), "layernorm_bwd_reduce")
+    _launch_jobs(LnReduceJob, LN_REDUCE_JOB_CAP, lib().ptamd_layernorm_bwd_reduce, "layernorm_bwd_reduce",
+                 (LnReduceJob(partials=ws.data_ptr(), D=D, dgamma=dg.data_ptr(), dbeta=db.data_ptr()) for ws, D, dg, db in pending))
     del pending[:]
 
 
@@ -447,53 +459,33 @@ def layernorm_bwd_dropout(dy, x, gamma, mean, rstd, dgamma, dbeta, dres, dropout
     T, D = x.shape
     dx = torch.empty_like(x)
     dropped = torch.empty_like(x) if dropout_p > 0 else None
-    if pending is not None and len(pending) >= 16:
-        layernorm_bwd_flush(pending)
-    ws = _ln_workspace(D, x.device, pending)
-    defer = pending is not None
     slabs, slab_stride = (dy.n, dy.stride) if isinstance(dy, Slabs) else (1, 0)    # (linear_bwd_input: defer_reduce)
-    check(lib().ptamd_layernorm_bwd_dropout(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), T, D, float(dropout_p),
-                                            int(seed), int(stream_id), ptr(dx), ptr(dropped), ptr(row_scale),
-                                            ptr(bound_factor), ptr(bound_scale), ptr(row_scale_min), ptr(bound_scale_min),
-                                            ptr(planes), None if defer else ptr(dgamma), None if defer else ptr(dbeta),
-                                            slabs, slab_stride, ptr(ws), ws.numel(),
-                                            stream()), "layernorm_bwd_dropout")
-    if defer:
-        pending.append((ws, D, dgamma, dbeta))
+    _ln_bwd_site(lambda dg, db, ws, ws_bytes: check(lib().ptamd_layernorm_bwd_dropout(
+        ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), T, D, float(dropout_p), int(seed), int(stream_id), ptr(dx),
+        ptr(dropped), ptr(row_scale), ptr(bound_factor), ptr(bound_scale), ptr(row_scale_min), ptr(bound_scale_min), ptr(planes),
+        dg, db, slabs, slab_stride, ws, ws_bytes, stream()), "layernorm_bwd_dropout"), D, x.device, dgamma, dbeta, pending)
     return dx, (dropped if dropped is not None else dx)
 
 
 def weight_scales(jobs):
     """jobs: list of dict(w=tensor view [rows, cols] (row stride ld), row_scale=, col_scale=, stats=) -> ptamd_weight_scales."""
-    from ._lib import WScaleJob
-    for i in range(0, len(jobs), 40):
-        chunk = jobs[i:i + 40]
-        arr = (WScaleJob * len(chunk))()
-        for k, j in enumerate(chunk):
-            w = j["w"]
-            rows, cols = (w.shape[0], w.shape[1]) if w.dim() == 2 else (1, w.shape[0])
-            arr[k] = WScaleJob(w=w.data_ptr(), rows=rows, cols=cols, ld=w.stride(0) if w.dim() == 2 else cols,
-                               row_scale=j["row_scale"].data_ptr() if j.get("row_scale") is not None else None,
-                               col_scale=j["col_scale"].data_ptr() if j.get("col_scale") is not None else None,
-                               stats=j["stats"].data_ptr() if j.get("stats") is not None else None,
-                               rows_only=int(bool(j.get("rows_only", False))))
-        check(lib().ptamd_weight_scales(arr, len(chunk), stream()), "weight_scales")
+    def job(j):
+        w = j["w"]
+        rows, cols = (w.shape[0], w.shape[1]) if w.dim() == 2 else (1, w.shape[0])
+        return WScaleJob(w=w.data_ptr(), rows=rows, cols=cols, ld=w.stride(0) if w.dim() == 2 else cols,
+                         row_scale=_addr(j.get("row_scale")), col_scale=_addr(j.get("col_scale")), stats=_addr(j.get("stats")),
+                         rows_only=int(bool(j.get("rows_only", False))))
+    _launch_jobs(WScaleJob, WSCALE_JOB_CAP, lib().ptamd_weight_scales, "weight_scales", map(job, jobs))
 
 
 def bound_scales(jobs):
     """jobs: list of dict(ln_gamma=, ln_beta=, w=, w_index=, bias=, sqrt_d=, post_scale=, out_scale=, out_value=) of stats
     records / outputs (tensors) -> ptamd_bound_scales."""
-    from ._lib import BoundJob
-    P = lambda t: t.data_ptr() if t is not None else None                     # noqa: E731
-    for i in range(0, len(jobs), 40):
-        chunk = jobs[i:i + 40]
-        arr = (BoundJob * len(chunk))()
-        for k, j in enumerate(chunk):
-            arr[k] = BoundJob(ln_gamma_stats=P(j.get("ln_gamma")), ln_beta_stats=P(j.get("ln_beta")), w_stats=P(j["w"]),
-                              w_stat_index=int(j["w_index"]), bias_stats=P(j.get("bias")), sqrt_d=float(j.get("sqrt_d", 0.0)),
-                              post_scale=float(j.get("post_scale", 1.0)), out_scale=P(j.get("out_scale")),
-                              out_value=P(j.get("out_value")))
-        check(lib().ptamd_bound_scales(arr, len(chunk), stream()), "bound_scales")
+    _launch_jobs(BoundJob, BOUND_JOB_CAP, lib().ptamd_bound_scales, "bound_scales", (
+        BoundJob(ln_gamma_stats=_addr(j.get("ln_gamma")), ln_beta_stats=_addr(j.get("ln_beta")), w_stats=_addr(j["w"]),
+                 w_stat_index=int(j["w_index"]), bias_stats=_addr(j.get("bias")), sqrt_d=float(j.get("sqrt_d", 0.0)),
+                 post_scale=float(j.get("post_scale", 1.0)), out_scale=_addr(j.get("out_scale")),
+                 out_value=_addr(j.get("out_value"))) for j in jobs))
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, pending=None):
@@ -501,15 +493,9 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, pending=No
     that collects the (dgamma, dbeta) reduction of this site for `layernorm_bwd_flush` instead of launching it here."""
     T, D = x.shape
     dx = torch.empty_like(x)
-    if pending is not None and len(pending) >= 16:
-        layernorm_bwd_flush(pending)
-    ws = _ln_workspace(D, x.device, pending)
-    defer = pending is not None
-    check(lib().ptamd_layernorm_bwd(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), T, D, ptr(dx),
-                                    None if defer else ptr(dgamma), None if defer else ptr(dbeta), ptr(ws), ws.numel(), stream()),
-          "layernorm_bwd")
-    if defer:
-        pending.append((ws, D, dgamma, dbeta))
+    _ln_bwd_site(lambda dg, db, ws, ws_bytes: check(lib().ptamd_layernorm_bwd(
+        ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), T, D, ptr(dx), dg, db, ws, ws_bytes, stream()),
+        "layernorm_bwd"), D, x.device, dgamma, dbeta, pending)
     return dx
 
 
@@ -530,7 +516,7 @@ def embed_bwd(seq, dout, D, dropout_p, seed, demb):
 
 
 def attention_bwd_reads_keep_bits(B, L, H, dk, arith):
-    return bool(lib().ptamd_attention_bwd_reads_keep_bits(B, L, H, dk, int(_DEFAULT_ARITH if arith is None else arith)))
+    return bool(lib().ptamd_attention_bwd_reads_keep_bits(B, L, H, dk, _arith(arith)))
 
 
 def attention_keep_bits(B, L, H, device):
@@ -540,7 +526,7 @@ def attention_keep_bits(B, L, H, device):
 
 def attention_reads_kv_planes(B, L, H, dk, arith):
     """True when the attention kernels of this shape and arithmetic read K / V pre-split (written by the QKV product's epilogue)."""
-    return bool(lib().ptamd_attention_reads_kv_planes(B, L, H, dk, int(_DEFAULT_ARITH if arith is None else arith)))
+    return bool(lib().ptamd_attention_reads_kv_planes(B, L, H, dk, _arith(arith)))
 
 
 def attention_kv_buffers(T, H, device):
@@ -557,7 +543,7 @@ def attention_fwd(qkv, seq, H, dropout_p, seed, stream_id, arith=None, keep_bits
     out = torch.empty(B * L, D, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(B, H, L, dtype=torch.float32, device=qkv.device)
     check(lib().ptamd_attention_fwd(ptr(qkv), ptr(seq), B, L, H, D // H, float(dropout_p), int(seed), int(stream_id),
-                                    int(_DEFAULT_ARITH if arith is None else arith), ptr(out), ptr(lse), ptr(keep_bits),
+                                    _arith(arith), ptr(out), ptr(lse), ptr(keep_bits),
                                     ptr(kv[0]) if kv is not None else None, ptr(kv[1]) if kv is not None else None,
                                     stream()), "attention_fwd")
     return out, lse
@@ -574,7 +560,7 @@ def attention_bwd(qkv, seq, out, dout, lse, H, dropout_p, seed, stream_id, arith
     ws = workspace("attn", lib().ptamd_attention_workspace_bytes(B, L, H, D // H), qkv.device)
     check(lib().ptamd_attention_bwd(ptr(qkv), ptr(seq), ptr(out), ptr(dout), ptr(lse), B, L, H, D // H,
                                     float(dropout_p), int(seed), int(stream_id),
-                                    int(_DEFAULT_ARITH if arith is None else arith), ptr(dqkv), ptr(row_scale),
+                                    _arith(arith), ptr(dqkv), ptr(row_scale),
                                     ptr(row_scale_min), ptr(keep_bits), ptr(kv[0]) if kv is not None else None,
                                     ptr(kv[1]) if kv is not None else None, ptr(ws), ws.numel(), stream()), "attention_bwd")
     return dqkv
@@ -626,14 +612,10 @@ def adam_step(w, g, m, v, sqnorm, max_norm, lr, beta1, beta2, eps, weight_decay,
 def fill_u32(jobs):
     """jobs: list of (int32 / uint32 / float32 tensor, value) -> every element of each tensor = value (its bit pattern), ONE
     launch for up to 8 contiguous tensors (ptamd_fill_u32)."""
-    from ._lib import FillJob
-    for i in range(0, len(jobs), 8):
-        chunk = jobs[i:i + 8]
-        arr = (FillJob * len(chunk))()
-        for k, (t, value) in enumerate(chunk):
-            assert t.is_contiguous() and t.element_size() == 4
-            arr[k] = FillJob(dst=t.data_ptr(), n=t.numel(), value=int(value) & 0xFFFFFFFF)
-        check(lib().ptamd_fill_u32(arr, len(chunk), stream()), "fill_u32")
+    def job(t, value):
+        assert t.is_contiguous() and t.element_size() == 4
+        return FillJob(dst=t.data_ptr(), n=t.numel(), value=int(value) & 0xFFFFFFFF)
+    _launch_jobs(FillJob, FILL_JOB_CAP, lib().ptamd_fill_u32, "fill_u32", (job(t, v) for t, v in jobs))
 
 
 # ----------------------------------------------------------------------------- conv-enc front end
@@ -690,6 +672,113 @@ def posenc_add_bwd(dy, dropout_p, seed):
 
 
 # ----------------------------------------------------------------------------- the weights of a step in one pass (csrc/wprep.hip)
+_PARITY = object()       # placeholder of WeightsPrep._call: "the copy that is due"
+
+
+def wprep_plan(numel, segs, groups, rows_per_block, plain_floats_per_block):
+    """The host tables of a `ptamd_wprep_plan` (include/ptamd.h) from the description `WeightsPrep` takes, with plain integers
+    for its tensors: row_scale / col_scale / out_scale / out_value are indices into `ints` / `values` (or None), row_planes /
+    col_planes device addresses (or None).  The block sizes are ptamd_wprep_rows_per_block() and
+    ptamd_wprep_plain_floats_per_block().  Integer arithmetic only: no device, no library.  Returns dict(segs [WprepSeg],
+    blocks_a [(segment | -(plain range + 1), block)], blocks_b [(kind, segment | group, block, 0)], plain [(first, floats)],
+    bounds [WprepBound], groups [(first bound, bounds, first colnorm entry, entries)], colnorm [segment], ncolmax, ncolsq,
+    n_matrix_blocks)."""
+    PANEL = 512                     # kernel A keeps whole rows in registers: wider matrices go through it as column panels
+    segs = sorted(segs, key=lambda s: s["offset"])
+    ix = lambda v: -1 if v is None else int(v)                                                          # noqa: E731
+    table, blocks_a, blocks_b, plain = [], [], [], []
+    ncolmax = ncolsq = 0            # entries of the pool of maxima (column maxima, row maxima of panelled matrices) / of colsq
+    rownorm_recs, panelled_recs = set(), set()      # statistics records fed by whole rows / by panels (maximum only)
+    pos = 0
+    for s in segs:
+        rows, cols, off = int(s["rows"]), int(s["cols"]), int(s["offset"])
+        if cols % 4 or off % 4 or off < pos or (cols > PANEL and cols % PANEL):
+            raise ValueError(f"ptamd_weights_prep: segment (offset {off}, {rows} x {cols}) is not representable")
+        if off > pos:
+            plain.append((pos, off - pos))
+        pos = off + rows * cols
+        want_cols = s.get("col_scale") is not None
+        for name in ("row_planes", "col_planes"):
+            if s.get(name) is not None and (rows % 32 or cols % 32):
+                raise ValueError("ptamd_weights_prep: planes need rows and cols that are multiples of 32")
+        if s.get("col_planes") is not None and not want_cols:
+            raise ValueError("ptamd_weights_prep: col_planes need col_scale")
+        if s.get("colnorm") and (s.get("stats") is None or not want_cols):
+            raise ValueError("ptamd_weights_prep: colnorm needs a statistics record and col_scale")
+        stats = -1 if s.get("stats") is None else int(s["stats"])
+        npanels = -(-cols // PANEL)
+        wide = npanels > 1
+        if wide and (s.get("row_planes") is not None or int(s.get("stats_row0", 0)) != 0):
+            raise ValueError("ptamd_weights_prep: a matrix wider than 512 columns cannot have row planes or a statistics sub-range")
+        if stats >= 0:
+            (panelled_recs if wide else rownorm_recs).add(stats)
+        colmax0 = ncolmax
+        ncolmax += cols if want_cols else 0
+        rowmax0 = -1
+        if wide and s.get("row_scale") is not None:
+            rowmax0 = ncolmax
+            ncolmax += rows
+        nrb = -(-rows // rows_per_block)
+        for pnl in range(npanels):
+            pc = min(PANEL, cols - pnl * PANEL)
+            k = len(table)
+            table.append(WprepSeg(
+                offset=off + pnl * PANEL, rows=rows, cols=pc, stats_row0=-1 if wide else int(s.get("stats_row0", 0)),
+                stats_index=stats, row_scale_index=-1 if wide else ix(s.get("row_scale")),
+                col_scale_index=ix(s.get("col_scale")) + pnl * PANEL if want_cols else -1,
+                colmax_index=colmax0 + pnl * PANEL if want_cols else 0, colsq_index=ncolsq if s.get("colnorm") else -1,
+                row_planes=s.get("row_planes") or 0, col_planes=0, ld=cols, rowmax_index=rowmax0))
+            blocks_a += [(k, b) for b in range(nrb)]
+            if want_cols:
+                blocks_b.append((0, k, 0, 0))
+            if s.get("colnorm"):
+                ncolsq += nrb * pc
+        if wide and rowmax0 >= 0 or s.get("col_planes") is not None:
+            # the matrix as a whole, for kernel B only (not in blocks_a): row scales of a panelled matrix, planes of its transpose
+            k = len(table)
+            table.append(WprepSeg(offset=off, rows=rows, cols=cols, stats_row0=0, stats_index=-1,
+                                  row_scale_index=ix(s.get("row_scale")) if wide else -1, col_scale_index=-1,
+                                  colmax_index=colmax0, colsq_index=-1, row_planes=0, col_planes=s.get("col_planes") or 0,
+                                  ld=cols, rowmax_index=rowmax0))
+            if rowmax0 >= 0:
+                blocks_b += [(3, k, b, 0) for b in range(-(-rows // 256))]
+            if s.get("col_planes") is not None:
+                nchunks = (cols // 32) * (-(-rows // 32) * 2) * 64           # rows of W^T = cols; 16-column blocks of its K = rows
+                blocks_b += [(1, k, b, 0) for b in range(-(-nchunks // 256))]
+    if pos < numel:
+        plain.append((pos, numel - pos))
+    n_matrix_blocks = len(blocks_a)
+    for j, (first, n) in enumerate(plain):
+        blocks_a += [(-(j + 1), b) for b in range(-(-n // plain_floats_per_block))]
+    # bound jobs, per group; the segments whose column norm a group needs are those flagged `colnorm` whose statistics
+    # record one of the group's jobs reads with w_index == 1
+    by_stats = {}
+    for k, t in enumerate(table):
+        if t.colsq_index >= 0:
+            by_stats.setdefault(int(t.stats_index), []).append(k)
+    bounds, grp_rows, cn_list = [], [], []
+    for g, jobs in enumerate(groups):
+        first, cn_first = len(bounds), len(cn_list)
+        for j in jobs:
+            # entry [0] of a record (the largest row norm) is what `w_index` 0 and `ln_beta` read: panels do not compute it
+            norms_read = ([int(j["w"])] if int(j["w_index"]) == 0 else []) + [ix(j.get("ln_beta"))]
+            if any(n in panelled_recs and n not in rownorm_recs for n in norms_read):
+                raise ValueError("ptamd_weights_prep: a bound job reads the row norm of a matrix wider than 512 columns, "
+                                 "which the pass does not compute")
+            bounds.append(WprepBound(ln_gamma_stats=ix(j.get("ln_gamma")), ln_beta_stats=ix(j.get("ln_beta")), w_stats=int(j["w"]),
+                                     w_stat_index=int(j["w_index"]), bias_stats=ix(j.get("bias")),
+                                     sqrt_d=float(j.get("sqrt_d", 0.0)), post_scale=float(j.get("post_scale", 1.0)),
+                                     out_scale=ix(j.get("out_scale")), out_value=ix(j.get("out_value"))))
+            if int(j["w_index"]) == 1 and int(j["w"]) in by_stats:
+                cn_list += [k for k in by_stats[int(j["w"])] if k not in cn_list[cn_first:]]
+        grp_rows.append((first, len(bounds) - first, cn_first, len(cn_list) - cn_first))
+        blocks_b.append((2, g, 0, 0))
+    if not groups:
+        raise ValueError("ptamd_weights_prep: at least one bounds group (it also resets the statistics)")
+    return dict(segs=table, blocks_a=blocks_a, blocks_b=blocks_b, plain=plain, bounds=bounds, groups=grp_rows, colnorm=cn_list,
+                ncolmax=ncolmax, ncolsq=ncolsq, n_matrix_blocks=n_matrix_blocks)
+
+
 class WeightsPrep:
     """Plan of ptamd_weights_prep / ptamd_sgd_step_prep / ptamd_adam_step_prep for one model: the device-resident tables of
     include/ptamd.h (`ptamd_wprep_plan`) built from a description of the flat parameter buffer.
@@ -704,107 +793,15 @@ class WeightsPrep:
     """
 
     def __init__(self, numel, segs, groups, ints, values, nstats):
-        import numpy as np
-        from ._lib import WprepBound, WprepPlan, WprepSeg
         dev = ints.device
-        RB, PF = lib().ptamd_wprep_rows_per_block(), lib().ptamd_wprep_plain_floats_per_block()
-        PANEL = 512                     # kernel A keeps whole rows in registers: wider matrices go through it as column panels
-        segs = sorted(segs, key=lambda s: s["offset"])
-        idx = lambda view, base: -1 if view is None else view.storage_offset() - base.storage_offset()       # noqa: E731
-        table, blocks_a, blocks_b, plain = [], [], [], []
-        ncolmax = ncolsq = 0            # entries of the pool of maxima (column maxima, row maxima of panelled matrices) / of colsq
-        rownorm_recs, panelled_recs = set(), set()      # statistics records fed by whole rows / by panels (maximum only)
-        pos = 0
-        for s in segs:
-            rows, cols, off = int(s["rows"]), int(s["cols"]), int(s["offset"])
-            if cols % 4 or off % 4 or off < pos or (cols > PANEL and cols % PANEL):
-                raise ValueError(f"ptamd_weights_prep: segment (offset {off}, {rows} x {cols}) is not representable")
-            if off > pos:
-                plain.append((pos, off - pos))
-            pos = off + rows * cols
-            want_cols = s.get("col_scale") is not None
-            for name in ("row_planes", "col_planes"):
-                if s.get(name) is not None and (rows % 32 or cols % 32):
-                    raise ValueError("ptamd_weights_prep: planes need rows and cols that are multiples of 32")
-            if s.get("col_planes") is not None and not want_cols:
-                raise ValueError("ptamd_weights_prep: col_planes need col_scale")
-            if s.get("colnorm") and (s.get("stats") is None or not want_cols):
-                raise ValueError("ptamd_weights_prep: colnorm needs a statistics record and col_scale")
-            stats = -1 if s.get("stats") is None else int(s["stats"])
-            npanels = -(-cols // PANEL)
-            wide = npanels > 1
-            if wide and (s.get("row_planes") is not None or int(s.get("stats_row0", 0)) != 0):
-                raise ValueError("ptamd_weights_prep: a matrix wider than 512 columns cannot have row planes or a statistics sub-range")
-            if stats >= 0:
-                (panelled_recs if wide else rownorm_recs).add(stats)
-            colmax0 = ncolmax
-            ncolmax += cols if want_cols else 0
-            rowmax0 = -1
-            if wide and s.get("row_scale") is not None:
-                rowmax0 = ncolmax
-                ncolmax += rows
-            nrb = -(-rows // RB)
-            for pnl in range(npanels):
-                pc = min(PANEL, cols - pnl * PANEL)
-                k = len(table)
-                table.append(WprepSeg(
-                    offset=off + pnl * PANEL, rows=rows, cols=pc, stats_row0=-1 if wide else int(s.get("stats_row0", 0)),
-                    stats_index=stats, row_scale_index=-1 if wide else idx(s.get("row_scale"), ints),
-                    col_scale_index=idx(s.get("col_scale"), ints) + pnl * PANEL if want_cols else -1,
-                    colmax_index=colmax0 + pnl * PANEL if want_cols else 0,
-                    colsq_index=ncolsq if s.get("colnorm") else -1,
-                    row_planes=0 if s.get("row_planes") is None else s["row_planes"].data_ptr(), col_planes=0,
-                    ld=cols, rowmax_index=rowmax0))
-                blocks_a += [(k, b) for b in range(nrb)]
-                if want_cols:
-                    blocks_b.append((0, k, 0, 0))
-                if s.get("colnorm"):
-                    ncolsq += nrb * pc
-            if wide and rowmax0 >= 0 or s.get("col_planes") is not None:
-                # the matrix as a whole, for kernel B only (not in blocks_a): row scales of a panelled matrix, planes of its transpose
-                k = len(table)
-                table.append(WprepSeg(offset=off, rows=rows, cols=cols, stats_row0=0, stats_index=-1,
-                                      row_scale_index=idx(s.get("row_scale"), ints) if wide else -1, col_scale_index=-1,
-                                      colmax_index=colmax0, colsq_index=-1, row_planes=0,
-                                      col_planes=0 if s.get("col_planes") is None else s["col_planes"].data_ptr(), ld=cols,
-                                      rowmax_index=rowmax0))
-                if rowmax0 >= 0:
-                    blocks_b += [(3, k, b, 0) for b in range(-(-rows // 256))]
-                if s.get("col_planes") is not None:
-                    nchunks = (cols // 32) * (-(-rows // 32) * 2) * 64           # rows of W^T = cols; 16-column blocks of its K = rows
-                    blocks_b += [(1, k, b, 0) for b in range(-(-nchunks // 256))]
-        if pos < numel:
-            plain.append((pos, numel - pos))
+        idx = lambda view, base: None if view is None else view.storage_offset() - base.storage_offset()     # noqa: E731
+        p = wprep_plan(
+            numel, [dict(s, row_scale=idx(s.get("row_scale"), ints), col_scale=idx(s.get("col_scale"), ints),
+                         row_planes=_addr(s.get("row_planes")), col_planes=_addr(s.get("col_planes"))) for s in segs],
+            [[dict(j, out_scale=idx(j.get("out_scale"), ints), out_value=idx(j.get("out_value"), values)) for j in jobs]
+             for jobs in groups], lib().ptamd_wprep_rows_per_block(), lib().ptamd_wprep_plain_floats_per_block())
+        table, blocks_a, blocks_b, plain, bounds, grp_rows, cn_list, ncolmax, ncolsq, n_matrix_blocks = p.values()
         arr = (WprepSeg * len(table))(*table)
-        n_matrix_blocks = len(blocks_a)
-        for j, (first, n) in enumerate(plain):
-            blocks_a += [(-(j + 1), b) for b in range(-(-n // PF))]
-        # bound jobs, per group; the segments whose column norm a group needs are those flagged `colnorm` whose statistics
-        # record one of the group's jobs reads with w_index == 1
-        by_stats = {}
-        for k, t in enumerate(table):
-            if t.colsq_index >= 0:
-                by_stats.setdefault(int(t.stats_index), []).append(k)
-        bounds, grp_rows, cn_list = [], [], []
-        rec = lambda v: -1 if v is None else int(v)                                                         # noqa: E731
-        for g, jobs in enumerate(groups):
-            first, cn_first = len(bounds), len(cn_list)
-            for j in jobs:
-                # entry [0] of a record (the largest row norm) is what `w_index` 0 and `ln_beta` read: panels do not compute it
-                norms_read = ([int(j["w"])] if int(j["w_index"]) == 0 else []) + [rec(j.get("ln_beta"))]
-                if any(n in panelled_recs and n not in rownorm_recs for n in norms_read):
-                    raise ValueError("ptamd_weights_prep: a bound job reads the row norm of a matrix wider than 512 columns, "
-                                     "which the pass does not compute")
-                bounds.append(WprepBound(ln_gamma_stats=rec(j.get("ln_gamma")), ln_beta_stats=rec(j.get("ln_beta")), w_stats=int(j["w"]),
-                                         w_stat_index=int(j["w_index"]), bias_stats=rec(j.get("bias")),
-                                         sqrt_d=float(j.get("sqrt_d", 0.0)), post_scale=float(j.get("post_scale", 1.0)),
-                                         out_scale=idx(j.get("out_scale"), ints), out_value=idx(j.get("out_value"), values)))
-                if int(j["w_index"]) == 1 and int(j["w"]) in by_stats:
-                    cn_list += [k for k in by_stats[int(j["w"])] if k not in cn_list[cn_first:]]
-            grp_rows.append((first, len(bounds) - first, cn_first, len(cn_list) - cn_first))
-            blocks_b.append((2, g, 0, 0))
-        if not groups:
-            raise ValueError("ptamd_weights_prep: at least one bounds group (it also resets the statistics)")
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt))).to(dev)           # noqa: E731
         self.t_segs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         self.t_blocks_a = up(blocks_a, np.int32).reshape(-1, 2)
@@ -817,9 +814,7 @@ class WeightsPrep:
         self.colmax = torch.zeros(2, max(ncolmax, 1), dtype=torch.int32, device=dev)
         self.colsq = torch.zeros(max(ncolsq, 2), dtype=torch.float64, device=dev)
         self.stats = torch.zeros(2, nstats, 4, dtype=torch.float32, device=dev)
-        self.ints, self.values = ints, values
-        self.parity = 0
-        self.numel = int(numel)
+        self.ints, self.values, self.parity, self.numel = ints, values, 0, int(numel)
         self.plan = WprepPlan(segs=self.t_segs.data_ptr(), nsegs=len(table), blocks_a=self.t_blocks_a.data_ptr(),
                               nblocks_a=len(blocks_a), nblocks_a_matrices=n_matrix_blocks, plain=self.t_plain.data_ptr(),
                               nplain=len(plain), blocks_b=self.t_blocks_b.data_ptr(), nblocks_b=len(blocks_b),
@@ -855,6 +850,3 @@ class WeightsPrep:
         self._call("adam_step_prep", lib().ptamd_adam_step_prep, with_planes, _PARITY, ptr(w), ptr(g), ptr(m), ptr(v), w.numel(),
                    ptr(sqnorm), float(max_norm or 0.0), float(lr), float(beta1), float(beta2), float(eps),
                    float(weight_decay), int(step), int(bool(zero_grad)), stream())
-
-
-_PARITY = object()       # placeholder of WeightsPrep._call: "the copy that is due"
