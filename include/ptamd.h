@@ -617,6 +617,53 @@ int ptamd_plddt_fwd(const float *logits, int ld, const float *target, int target
 int ptamd_plddt_bwd(const float *logits, int ld, const float *target, int target_stride, int64_t T, int nbins, const float *sums,
                     float coef, float *dlogits, int ldd, void *stream);
 
+/* Pair sweep of the trained PAE head (csrc/pae_head.hip; protein_transformer_amd/confidence.py, class PaeHead): the aligned-error
+ * head of AlphaFold 2 (Jumper et al., Nature 596:583-589 (2021), supplementary 1.9.7) without its relative-position features - a
+ * softmax over nbins bins of 1 / bins_per_angstrom A each, the last one open, for every (frame i, point j) of a protein, trained
+ * by cross-entropy against the bin of the true aligned error of the model's own prediction (ptamd_aligned_error with K = 1, the
+ * truth as the reference).  Not in the reference.
+ *   uv [B*L, lduv] in: row b * L + i holds u_i (the frame side) in the columns 0 .. H-1 and v_i (the point side) in H .. 2H-1;
+ *     lduv >= 2H is a row stride in floats and the spare columns are never read.  H a multiple of 4 in 4 .. 64.
+ *   w2 [nbins, H], b2 [nbins] in, 2 <= nbins <= 64.  z_ij = relu(u_i + v_j), logits_ij = w2 z_ij + b2, p the max-subtracted
+ *     softmax of the pair's nbins logits, c_k = (k + 0.5) / bins_per_angstrom the centre of bin k.
+ *   seq [B,L]: residue i is PRESENT when seq[i] is in 0..19, the rule of ptamd_ensemble_spread; n_b is the number of present
+ *     residues and pair (i, j) is DEFINED when both are present, the diagonal included.
+ *   pae [B,L,L] out: sum_k p_k c_k on every defined pair, NaN on every other and in padded rows and columns; every one of the
+ *     B * L * L elements is written.
+ *   stats [B,2] out: {mean, ptm}.  mean is the mean of the defined entries of pae; ptm = max over the present i of
+ *     (1 / n_b) sum over the present j of sum_k p_k / (1 + (c_k / d0)^2), d0 = 1.24 cbrt(max(n_b, 19) - 15) - 1.8: the d0 of
+ *     ptamd_aligned_error, but the formula APPLIED TO THE PREDICTED DISTRIBUTION and not to a mean error.  Both NaN when n_b = 0.
+ *   target [B,L,L] in, or NULL.  A pair COUNTS when it is defined and its target is finite; its bin is min(nbins - 1, max(0,
+ *     (int)floorf(target * bins_per_angstrom))), the product one fp32 multiply (the rule of ptamd_plddt_fwd).
+ *     sums [2] out: {mean of -log p_bin over the counted pairs of the whole batch (NaN when there is none), their number}.
+ *     NULL is inference: sums and the workspace may be NULL and nothing but pae and stats is written.
+ *   ptamd_pae_head_bwd: with g_ijk = coef / sums[1] * (p_k - [k == bin_ij]) on the counted pairs and 0 elsewhere,
+ *     db2 = sum g, dw2[k,h] = sum_ij g_ijk z_ijh, dz_ij = w2^T g_ij masked by z_ijh > 0 (the derivative at exactly 0 is 0),
+ *     du_i = sum_j dz_ij into duv[:, :H], dv_j = sum_i dz_ij into duv[:, H:2H].  All B * L * ldd floats of duv (ldd >= 2H) are
+ *     written: the spare columns, absent residues and padding are exactly +0 (whatever the sign of coef), and so is everything
+ *     when sums[1] is 0.  sums is
+ *     what ptamd_pae_head_fwd left, read on the device (no host synchronisation).  dw2 and db2 are overwritten.
+ * Logits are formed pair by pair and formed again in the backward pass: nothing of size L * L * nbins or L * L * H is stored.
+ * The workspace (ptamd_pae_head_workspace_bytes, a function of (B, L, H, nbins) only, the larger of the two passes' needs) holds
+ * a 32-byte record per residue in the forward pass and, in the backward pass, partial sums of dv, dw2 and db2 per (protein, one
+ * of a fixed number of frame slabs): it grows with B * L * H, not with L^2.  fp32 products and softmax; the sums along j of a
+ * row of pae, of the pTM term and of the cross-entropy are fp64 in the order j = 0 .. L-1, the rows and then the proteins are
+ * added in fp64 in index order and every result is rounded to fp32 once; the gradient partials are fp32 and are added in fp64 in
+ * index order.  No atomics, no order-dependent reduction: two calls give the same bits, and pae and stats of a protein depend
+ * neither on the batch around it nor on how far its row is padded.  B or L <= 0, B beyond 65535 or B * L beyond INT_MAX (what one
+ * launch addresses), H outside 4 .. 64 or no multiple of 4, nbins outside 2 .. 64, lduv or ldd below 2H, bins_per_angstrom not
+ * finite and positive, a NULL array that the call would read or write: PTAMD_ERR_BAD_SHAPE (a size of 0); where the call uses a
+ * workspace (the backward pass, the forward pass with a target), one that is NULL or too small: PTAMD_ERR_WORKSPACE, not 16-byte
+ * aligned: PTAMD_ERR_ALIGN; nothing is launched or written then.  Nothing is allocated, no state between calls, nothing read
+ * from the environment. */
+size_t ptamd_pae_head_workspace_bytes(int B, int L, int H, int nbins);
+int ptamd_pae_head_fwd(const float *uv, int lduv, const float *w2, const float *b2, const int64_t *seq, const float *target, int B,
+                       int L, int H, int nbins, float bins_per_angstrom, float *pae, float *stats, float *sums, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ptamd_pae_head_bwd(const float *uv, int lduv, const float *w2, const float *b2, const int64_t *seq, const float *target, int B,
+                       int L, int H, int nbins, float bins_per_angstrom, const float *sums, float coef, float *duv, int ldd,
+                       float *dw2, float *db2, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ encoder building blocks
  * Row-major fp32 GEMM on the matrix cores (the `arith` field selects the arithmetic, see PTAMD_GEMM_* below):
  *     C[M,N] = epilogue( A (*) B )          with reduction length K

@@ -160,6 +160,9 @@ SIGNATURES = {
     "ptamd_plddt_workspace_bytes": (_sz, [_i64]),
     "ptamd_plddt_fwd": (_i, [_p, _i, _p, _i, _i64, _i, _p, _p, _p, _p, _sz, _p]),
     "ptamd_plddt_bwd": (_i, [_p, _i, _p, _i, _i64, _i, _p, _f, _p, _i, _p]),
+    "ptamd_pae_head_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ptamd_pae_head_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "ptamd_pae_head_bwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _f, _p, _i, _p, _p, _p, _sz, _p]),
     "ptamd_gemm_workspace_bytes": (_sz, [_i, _i, _i]),
     "ptamd_gate_mask_bytes": (_sz, [_i, _i]),
     "ptamd_gemm": (_i, [C.POINTER(GemmArgs), _p]),

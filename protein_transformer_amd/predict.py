@@ -1,7 +1,7 @@
 """Predict all-atom structures from amino-acid sequences with a trained checkpoint, with a dropout-ensemble confidence.
 
     python -m protein_transformer_amd.predict CHECKPOINT SEQS.fasta --out DIR [--samples 8] [--seed 0] [--batch_residues 16384]
-                                              [--per_residue] [--pae] [--plddt]
+                                              [--per_residue] [--pae] [--plddt] [--ptm]
 
 reads a checkpoint that `train.checkpoint_model` wrote and a multi-record FASTA file, and for every sequence writes
 `DIR/<identifier>.pdb` - the structure of the deterministic (`model.eval()`) pass, built by the NeRF kernels - and prints one JSON
@@ -22,8 +22,15 @@ sample gets no file.  One further read back per batch.
 factor of every atom is then its residue's pLDDT, `plddt` (the mean over the residues) is appended to the JSON line and
 `--per_residue` gains a last column `plddt`.
 
+`--ptm` (needs a checkpoint with a PAE head, written by `python -m protein_transformer_amd.confidence fit-pae`; works with
+`--samples 0`; independent of `--pae` and `--plddt`) runs that head on the same hidden state: `DIR/<identifier>.head_pae.json` is
+the head's expected aligned error in the same AlphaFold DB layout, and `pae` (its mean) and `ptm` (the pTM formula applied to the
+head's predicted DISTRIBUTION of errors) are appended to the JSON line.  One further read back per batch.  A head is as good as its
+fit: `confidence calibrate --pae` measures it, and nobody has measured it on a really trained model yet.
+
 `ens-pae` and `ens-ptm`, like `ens-lddt`, measure the dropout ensemble's SELF-CONSISTENCY: they are NOT calibrated predictions of
-the true aligned error or TM-score, and how well they track them has not been measured on any trained model.
+the true aligned error or TM-score; how well they track them is what `confidence calibrate --pae --samples K` measures, and that
+has not been done on any trained model.
 
 `ens-lddt` (and, without `--plddt`, the temperature factors) is a dropout SELF-CONSISTENCY score on the lDDT scale - 100 x the mean
 lDDT-C-alpha of the samples against the written structure - NOT a calibrated pLDDT.  How well it, or the head's `plddt`, tracks the
@@ -44,6 +51,7 @@ from .protein.Sequence import AA_MAP, ONE_TO_THREE_LETTER_MAP, VOCAB
 KEYS = ("id", "n-res", "ens-lddt", "ens-rmsd", "ens-rmsf-ca", "usable", "samples")
 PAE_KEYS = ("ens-pae", "ens-ptm")                                 # appended to KEYS by --pae
 PLDDT_KEYS = ("plddt",)                                           # appended by --plddt, behind PAE_KEYS
+PTM_KEYS = ("pae", "ptm")                                         # appended by --ptm, behind PLDDT_KEYS
 PER_RESIDUE_HEADER = ("resnum", "resname", "conf", "rmsf_ca", "rmsf_all")
 PLDDT_COLUMN = "plddt"                                            # last column of --per_residue under --plddt
 
@@ -126,12 +134,13 @@ def load_checkpoint(path, device=None):
     return model.to(device)
 
 
-def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None, pae=False, head=None):
+def predict_records(model, records, samples=8, seed=0, batch_residues=16384, device=None, pae=False, head=None, pae_head=None):
     """records [(identifier, sequence)] -> per record, in input order, dict(crd [n*14, 3], conf, rmsf_ca, rmsf_all [n], rmsd [K],
     usable) as host arrays (the ensemble fields None with samples = 0).  One upload and one read back per batch.  `pae` (needs
     samples >= 1): also ae [n, n] and ae_stats [2] = {mean, tm}, from one further read back per batch.  `head` (a
     `confidence.ConfidenceHead`): also plddt [n], the head on the last hidden state of the deterministic pass, in the same read
-    back."""
+    back.  `pae_head` (a `confidence.PaeHead`): also head_pae [n, n] and head_pae_stats [2] = {mean, ptm}, from one further read
+    back per batch."""
     from .confidence import mask_padding
     from .ensemble import predict_ensemble
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -143,7 +152,8 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
         for row, i in enumerate(batch):
             ids[row, :len(records[i][1])] = [AA_MAP[c] for c in records[i][1]]
         seq = torch.from_numpy(ids).to(dev)
-        ens = predict_ensemble(model, seq, samples=K, seed=seed, aligned_error=bool(pae), hidden=head is not None)
+        ens = predict_ensemble(model, seq, samples=K, seed=seed, aligned_error=bool(pae),
+                               hidden=head is not None or pae_head is not None)
         fields = [ens.crd.reshape(B, -1)]
         if K:
             fields += [ens.conf, ens.rmsf.reshape(B, -1), ens.rmsd, ens.usable.float()[:, None]]
@@ -152,6 +162,9 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
         host = torch.cat(fields, dim=1).cpu().numpy()                                    # one read back
         if pae:
             matrix = torch.cat([ens.ae.reshape(B, -1), ens.ae_stats], dim=1).cpu().numpy()   # and the one of --pae
+        if pae_head is not None:
+            head_pae, head_stats, _ = pae_head.forward(ens.hidden, seq)
+            head_matrix = torch.cat([head_pae.reshape(B, -1), head_stats], dim=1).cpu().numpy()   # and the one of --ptm
         n_crd = L * NUM_PREDICTED_COORDS * 3
         for row, i in enumerate(batch):
             n = len(records[i][1])
@@ -165,6 +178,8 @@ def predict_records(model, records, samples=8, seed=0, batch_residues=16384, dev
                 r.update(plddt=host[row, host.shape[1] - L:host.shape[1] - L + n])
             if pae:
                 r.update(ae=matrix[row, :L * L].reshape(L, L)[:n, :n], ae_stats=matrix[row, L * L:])
+            if pae_head is not None:
+                r.update(head_pae=head_matrix[row, :L * L].reshape(L, L)[:n, :n], head_pae_stats=head_matrix[row, L * L:])
             out[i] = r
     return out
 
@@ -183,6 +198,11 @@ def summary(name, seq, r, samples):
 def pae_summary(r):
     mean, tm = (float(v) for v in r["ae_stats"])
     return {"ens-pae": mean if np.isfinite(mean) else None, "ens-ptm": tm if np.isfinite(tm) else None}
+
+
+def ptm_summary(r):
+    mean, ptm = (float(v) for v in r["head_pae_stats"])
+    return {"pae": mean if np.isfinite(mean) else None, "ptm": ptm if np.isfinite(ptm) else None}
 
 
 def pae_document(ae):
@@ -238,6 +258,10 @@ def parser():
     ap.add_argument("--plddt", action="store_true",
                     help="run the checkpoint's confidence head (`confidence fit`) on the deterministic pass: temperature factors = "
                          "pLDDT, `plddt` on the JSON line, a last column `plddt` under --per_residue; works with --samples 0")
+    ap.add_argument("--ptm", action="store_true",
+                    help="run the checkpoint's PAE head (`confidence fit-pae`) on the deterministic pass: write "
+                         "<identifier>.head_pae.json (AlphaFold DB layout) and add `pae` and `ptm` to the JSON line; works with "
+                         "--samples 0")
     return ap
 
 
@@ -249,11 +273,14 @@ def main(argv=None):
         if args.pae and args.samples < 1:
             raise ValueError("--pae is made of the dropout samples and needs --samples >= 1")
         records = read_fasta(args.fasta)
-        entry = None
-        if args.plddt:                               # (decided on the host, before the model is built)
-            from .confidence import head_from_entry, read_head_entry
-            entry = read_head_entry(args.checkpoint)
-            if entry is None:
+        entry = pae_entry = None
+        if args.plddt or args.ptm:                   # (decided on the host, before the model is built)
+            from .confidence import head_from_entry, pae_head_from_entry, read_head_entries
+            entry, pae_entry = read_head_entries(args.checkpoint)
+            if args.ptm and pae_entry is None:
+                raise ValueError(f"{args.checkpoint}: --ptm needs a checkpoint with a PAE head, and this one has none "
+                                 "(`python -m protein_transformer_amd.confidence fit-pae` writes one)")
+            if args.plddt and entry is None:
                 raise ValueError(f"{args.checkpoint}: --plddt needs a checkpoint with a confidence head, and this one has none "
                                  "(`python -m protein_transformer_amd.confidence fit` writes one)")
         model = load_checkpoint(args.checkpoint)
@@ -267,8 +294,11 @@ def main(argv=None):
         print(f"predict: {e}", file=sys.stderr)
         return 2
     os.makedirs(args.out, exist_ok=True)
-    head = head_from_entry(entry, next(model.parameters()).device) if entry is not None else None
-    results = predict_records(model, records, args.samples, args.seed, args.batch_residues, pae=args.pae, head=head)
+    dev = next(model.parameters()).device
+    head = head_from_entry(entry, dev) if args.plddt else None
+    pae_head = pae_head_from_entry(pae_entry, dev) if args.ptm else None
+    results = predict_records(model, records, args.samples, args.seed, args.batch_residues, pae=args.pae, head=head,
+                              pae_head=pae_head)
     for (name, seq), r in zip(records, results):
         PDB_Creator(r["crd"], seq=seq, b_factors=b_factors(r, len(seq))).save_pdb(os.path.join(args.out, name + ".pdb"), title=name)
         if args.per_residue:
@@ -280,6 +310,9 @@ def main(argv=None):
                 write_pae(os.path.join(args.out, name + ".pae.json"), r["ae"])
         if args.plddt:
             line[PLDDT_KEYS[0]] = _finite_mean(r["plddt"])
+        if args.ptm:
+            line.update(ptm_summary(r))
+            write_pae(os.path.join(args.out, name + ".head_pae.json"), r["head_pae"])
         print(json.dumps(line))
     return 0
 
