@@ -1068,14 +1068,23 @@ int ptamd_dropout_bwd(const float *dy, int64_t rows, int cols, float dropout_p, 
  *   col [T, k*Cp] = im2col(x [T, C], row stride ldx)   with Cp = C rounded up to 4 (zero padded), k odd
  *   y   [T, Co]   = col @ W2^T + bias                  W2 [Co, k*Cp] = pack(W [Co, C, k])
  *   dx = col2im(dy @ W2),  dW += unpack(dy^T @ col),  db += colsum(dy)
- * Windows never cross a protein boundary (rows are grouped in B proteins of L residues). */
+ * Windows never cross a protein boundary (rows are grouped in B proteins of L residues): a window slot outside its protein and
+ * the channels C .. Cp-1 of col and W2 are +0.  C need not be a multiple of 4 (ldx must be, and x 16-byte aligned).
+ * Spare columns are never read: C .. ldx-1 of x, the channels C .. Cp-1 of dcol and of dW2, and no row of x outside the B*L.
+ * col2im writes columns 0 .. C-1 of dx only: C .. lddx-1 keep what they held.
+ * PTAMD_ERR_BAD_SHAPE, with nothing launched: a count <= 0, an even k, ldx not a multiple of 4, ldx < C, lddx < C, a NULL array
+ * (im2col, col2im). */
 int ptamd_im2col1d(const float *x, int ldx, int B, int L, int C, int k, float *col, void *stream);
 int ptamd_col2im1d(const float *dcol, int B, int L, int C, int k, float *dx, int lddx, void *stream);
 int ptamd_conv_weight_pack(const float *w, int Co, int C, int k, float *w2, void *stream);
 int ptamd_conv_weight_unpack_add(const float *dw2, int Co, int C, int k, float *dw, void *stream);
-/* x [T, Cp] = one_hot(seq, C) (convolutional_encoder.py:110-111, use_embedding=False) */
+/* x [T, Cp] = one_hot(seq, C) (convolutional_encoder.py:110-111, use_embedding=False): x[t, c] = 1 where c == seq[t] and c < C.
+ * The row of an id outside 0 .. C-1 is all zeros, and the padding columns C .. Cp-1 are zero for every id. */
 int ptamd_onehot(const int64_t *seq, int64_t T, int C, float *x, void *stream);
-/* y = x + dropout(x + pe[pos]) and its adjoint (convolutional_encoder.py:118-119 with Sublayers.py:59-62) */
+/* y = x + dropout(x + pe[pos]), pos = t mod L, and its adjoint dx = dy (1 + keep / (1-p)) (convolutional_encoder.py:118-119 with
+ * Sublayers.py:59-62).  D and n are multiples of 4; rows L .. of pe are not read.  The dropout draws from stream 0xE3 of the
+ * counter hash pt_rand4 of csrc/common.h: word j of the generator call i = t*(D/4) + c/4 serves column (c & ~3) + j, and an
+ * element is kept iff its word >= uint32(p * 2^32) (all 32 bits; saturating at 2^32 - 1); p <= 0 draws nothing. */
 int ptamd_posenc_add_fwd(const float *x, const float *pe, int B, int L, int D, float dropout_p, uint64_t seed, float *y,
                          void *stream);
 int ptamd_posenc_add_bwd(const float *dy, int64_t n, float dropout_p, uint64_t seed, float *dx, void *stream);

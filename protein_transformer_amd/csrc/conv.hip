@@ -66,12 +66,13 @@ __global__ void conv_unpack_add_kernel(const float *__restrict__ dw2, int Co, in
   dw[i] += dw2[(size_t)co * (k * Cp) + j * Cp + c];
 }
 
-// one-hot rows: x [T, Cp] = (c == seq[t])
-__global__ void onehot_kernel(const int64_t *__restrict__ seq, int64_t T, int Cp, float *__restrict__ x) {
+// one-hot rows: x [T, Cp] = (c < C && c == seq[t]): the padding columns C .. Cp-1 are 0 for every id, a row whose id lies
+// outside 0 .. C-1 is all zeros
+__global__ void onehot_kernel(const int64_t *__restrict__ seq, int64_t T, int C, int Cp, float *__restrict__ x) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= T * Cp) return;
-  const int64_t t = i / Cp;
-  x[i] = (int64_t)(i - t * Cp) == seq[t] ? 1.f : 0.f;
+  const int64_t t = i / Cp, c = i - t * Cp;
+  x[i] = c < C && c == seq[t] ? 1.f : 0.f;
 }
 
 // y = x + dropout(x + pe[l])   (convolutional_encoder.py:118-119 with Sublayers.py:59-62); 4 channels per thread
@@ -123,7 +124,7 @@ __global__ void posenc_add_bwd_kernel(const float *__restrict__ dy, int64_t n4, 
 extern "C" {
 
 int ptamd_im2col1d(const float *x, int ldx, int B, int L, int C, int k, float *col, void *stream) {
-  if (B <= 0 || L <= 0 || C <= 0 || k <= 0 || !(k & 1) || (ldx & 3)) return PTAMD_ERR_BAD_SHAPE;
+  if (B <= 0 || L <= 0 || C <= 0 || k <= 0 || !(k & 1) || (ldx & 3) || ldx < C || !x || !col) return PTAMD_ERR_BAD_SHAPE;
   const int Cp = (C + 3) & ~3;
   const int64_t n4 = (int64_t)B * L * k * (Cp >> 2);
   hipLaunchKernelGGL(im2col1d_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, L, C,
@@ -132,7 +133,7 @@ int ptamd_im2col1d(const float *x, int ldx, int B, int L, int C, int k, float *c
 }
 
 int ptamd_col2im1d(const float *dcol, int B, int L, int C, int k, float *dx, int lddx, void *stream) {
-  if (B <= 0 || L <= 0 || C <= 0 || k <= 0 || !(k & 1)) return PTAMD_ERR_BAD_SHAPE;
+  if (B <= 0 || L <= 0 || C <= 0 || k <= 0 || !(k & 1) || lddx < C || !dcol || !dx) return PTAMD_ERR_BAD_SHAPE;
   const int Cp = (C + 3) & ~3;
   const int64_t n = (int64_t)B * L * C;
   hipLaunchKernelGGL(col2im1d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dcol, L, C, Cp,
@@ -157,7 +158,8 @@ int ptamd_conv_weight_unpack_add(const float *dw2, int Co, int C, int k, float *
 int ptamd_onehot(const int64_t *seq, int64_t T, int C, float *x, void *stream) {
   if (T <= 0 || C <= 0) return PTAMD_ERR_BAD_SHAPE;
   const int Cp = (C + 3) & ~3;
-  hipLaunchKernelGGL(onehot_kernel, dim3((unsigned)((T * Cp + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seq, T, Cp, x);
+  hipLaunchKernelGGL(onehot_kernel, dim3((unsigned)((T * Cp + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seq, T, C, Cp,
+                     x);
   return pt_check_launch();
 }
 
